@@ -13,8 +13,13 @@ no collective inside the fit; one all_gather of the fitted parameters at the end
 whole-job frames/s = frames of the K batches / max-over-ranks wall clock.  `--mode weak` is the former per-rank form (every
 rank fits its own K full batches).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline only: set-up, warm-up, the K timed steps, the result line.  `--full` adds what is measured beside it: the
+informational legs after the timed region (kernel alone + box calibration, full schedule, SMPL-T pre-fit, strict fp32, SIF-Net inference, demo
+pipeline), the CPU baseline and, with N > 1 ranks, the second timed pass with the run-time hand-out.  `--dump-outputs DIR` writes what the last
+timed step returned (fitted parameters and loss histories of batch K - 1) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -387,6 +392,16 @@ def cpu_baseline(syn, model, regs, pri, dec, labels, smpl_steps, obj_steps, budg
                       f"object-stage steps ({t_obj:.3f} s/step, N={N_OBJ}); scaled to the {smpl_steps}+{obj_steps} Adam steps/batch the GPU run executed"}
 
 
+def dump_outputs(out_dir, d, r):
+    """--dump-outputs: what the hot path hands back for one batch -- the parameters both stages updated in place and each stage's loss history over
+    the Adam steps it executed -- as <out_dir>/<name>.npy (parameters float32, losses float64; ~80 KB for a 96-frame batch)"""
+    os.makedirs(out_dir, exist_ok=True)
+    for k in ("pose", "betas", "trans", "obj_R", "obj_t", "obj_s"):
+        np.save(os.path.join(out_dir, k + ".npy"), d[k].detach().float().cpu().numpy())
+    for k, res in (("smpl_stage_losses", r[0]), ("object_stage_losses", r[1])):
+        np.save(os.path.join(out_dir, k + ".npy"), np.asarray(res.losses, np.float64)[:res.steps])
+
+
 def main():
     # watchdog (off by default; VT_BENCH_WATCHDOG=<seconds>): a run that is still alive after that many seconds dumps the Python stack of every thread to stderr and
     # exits with status 3 -- a hang (a rank waiting in a collective the others skipped, a leg stuck in a lock) then costs a bounded time and says WHERE it was
@@ -401,7 +416,11 @@ def main():
     ap.add_argument("--mode", choices=("strong", "weak"), default="strong",
                     help="strong (default): the K batches of ONE sequence sharded over the ranks; weak: every rank fits its own K full batches")
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run what is measured beside the headline: the informational legs, the CPU baseline and (N > 1) "
+                                                        "the run-time hand-out pass; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the fitted parameters and loss histories of the last timed step "
+                                                                        "(batch K - 1) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--res-scale", type=float, default=1.0, help="feature map resolution scale (1.0 = reference sizes)")
     ap.add_argument("--streams", type=int, default=3, help="batches in flight per GPU (one host thread + one HIP stream each).  Round 5, the driver's command on two leases: "
                                                            "2 streams 142.6-143.9 frames/s, 3 streams 145.3-147.1, 4 streams 142.4 (profiles/r05_streams_ab.txt)")
@@ -413,7 +432,7 @@ def main():
                     help="batch: every stream fits whole batches (SMPL stage, then object stage); staged: --streams streams run the SMPL stages, one more "
                          "stream runs the object stage of every batch as soon as its SMPL stage is done (the chip-filling query launches of one stage "
                          "beside the small silhouette / rigid-transform launches of the other)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the informational legs after the timed region (kernel alone, full schedule, "
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the informational legs after the timed region (kernel alone, full schedule, "
                                                               "SIF-Net inference = configs[3], demo pipeline = configs[4])")
     ap.add_argument("--pipeline-frames", type=int, default=1500)
     ap.add_argument("--handout", choices=("auto", "static", "dynamic"), default="auto",
@@ -432,14 +451,15 @@ def main():
 
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0")); local = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus > 1 and "RANK" not in os.environ:
-        # plain ``python bench.py --gpus N`` (no launcher): re-exec under torch.distributed.run, one rank per GPU on 127.0.0.1 -- the command a driver would
-        # otherwise have to spell out (a usage error here would lose the first real multi-GPU run)
+        # plain ``python bench.py --gpus N`` (no launcher): run again under torch.distributed.run in a child process, one rank per GPU on 127.0.0.1 -- the
+        # command a driver would otherwise have to spell out (a usage error here would lose the first real multi-GPU run)
         import socket
+        import subprocess
         with socket.socket() as s_:
             s_.bind(("127.0.0.1", 0)); port = s_.getsockname()[1]
         sys.stdout.flush(); sys.stderr.flush()
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
-                                  "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
+                                  "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
     # test hook (tests / dry runs on a 1-GPU box only): all ranks share GPU 0 and the collectives go through gloo on host copies
     shared_gpu = os.environ.get("VT_BENCH_TEST_SHARED_GPU") == "1"
     if shared_gpu:
@@ -676,6 +696,11 @@ def main():
         rank_jobs = [list(my_jobs)]
     if os.environ.get("VT_BENCH_DUMP_ROWS") and rank == 0:
         np.save(os.environ["VT_BENCH_DUMP_ROWS"], (job_rows if job_rows is not None else torch.cat([rows_of(d) for d in batches])).cpu().numpy())
+    if args.dump_outputs:
+        # the last timed step = job K - 1, written by the rank that fitted it (weak mode: rank 0's own last batch)
+        pos = my_jobs.index(args.steps - 1) if (args.steps - 1) in my_jobs else None
+        if pos is not None and pos in fitted and (strong or rank == 0):
+            dump_outputs(args.dump_outputs, batches[pos], results[pos])
     results = [results[i] for i in fitted]
     batch_frames = [int(batches[i]["pose"].shape[0]) for i in fitted]        # plain ints: nothing below may keep a batch alive (the informational legs release them)
     if use_dist:
@@ -692,7 +717,7 @@ def main():
                       "group_ranks": int(one.item()), "rank_devices": names}
 
     dyn_leg = None
-    if strong and use_dist and world > 1 and args.handout == "auto" and fits and not os.environ.get("VT_BENCH_NO_DYNAMIC_LEG"):
+    if args.full and strong and use_dist and world > 1 and args.handout == "auto" and fits and not os.environ.get("VT_BENCH_NO_DYNAMIC_LEG"):
         # second timed pass, reported beside the headline: the same K batches (fresh copies) handed out at run time -- early stop makes batches uneven
         # (282 + 452 .. 1030 + 1550 Adam steps), a shared counter evens the ranks out at the price of every rank holding all K inputs
         order = sorted(range(args.steps), key=lambda j: -job_frames[j]); packed2 = None
@@ -742,7 +767,7 @@ def main():
             del batches2
 
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # informational legs, all OUTSIDE the timed region; a failing leg is reported, never fatal for the headline line
         def leg(name, fn):
             try:
@@ -898,7 +923,7 @@ def main():
         for k in ("full_schedule", "smplt_prefit", "strict_fp32", "sifnet_inference", "hbm_allocated_before_pipeline_gb", "demo_pipeline"):
             if k in extras:
                 line[k] = extras[k]
-        if not args.no_cpu_baseline and world == 1:          # reported at N = 1 only (rank 0's host cores)
+        if args.full and not args.no_cpu_baseline and world == 1:          # reported at N = 1 only (rank 0's host cores)
             try:        # the CPU leg gets the host's default huge-page policy back (the library switched it off for the launch path: _lib._host_tuning)
                 import ctypes
                 ctypes.CDLL(None).prctl(41, 0, 0, 0, 0)

@@ -141,7 +141,7 @@ def test_bench_eight_ranks_on_one_gpu(tmp_path):
     MAX-reduced time, and the second timed pass with the run-time hand-out -- every job fitted exactly once -- return rows BIT-IDENTICAL to one rank's
     (recon_fit_base.py:411-419: a batch is an independent unit, who fits it cannot matter)."""
     import numpy as np
-    base = [os.path.join(ROOT, "bench.py"), "--warmup", "0", "--no-cpu-baseline", "--no-extras", "--streams", "1", "--steps", "20", "--res-scale", "0.125"]
+    base = [os.path.join(ROOT, "bench.py"), "--full", "--warmup", "0", "--no-cpu-baseline", "--no-extras", "--streams", "1", "--steps", "20", "--res-scale", "0.125"]
     lines = {}
     for tag, n, port in (("one", 1, 29581), ("eight", 8, 29582)):
         env = dict(os.environ, VT_BENCH_WATCHDOG="600", MASTER_ADDR="127.0.0.1", VT_BENCH_DUMP_ROWS=str(tmp_path / f"{tag}.npy"), OMP_NUM_THREADS="4")
