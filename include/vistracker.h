@@ -512,6 +512,39 @@ int vt_gen_scatter_heads(const float *pred, int B, int C, int kmax, const long l
 int vt_gen_resample(const float *samples, const int *order, const long long *cnt, const float *init, int B, int S, int S0, const float *u,
                     const float *pert, int M, float near_scale, float *out, void *stream);
 
+/* ---- shaded rendering of the fitted meshes (demo.sh step 7: render/render_side_comp.py:71-98 RendererSide2side.render_recon ->
+ * render/nr_utils.py:681-702 NrWrapper.render / render_meshes -> neural_renderer.Renderer.render, RGB mode) ---------------------------------------------
+ * PARITY UNPINNED: neural_renderer is third-party; the rule (restated in render.hip's header, held to an independent float64 renderer in
+ * tests/test_gpu_render.py): fill_back doubling (reversed copy [i2,i1,i0], same colour; doubled id f / F + f of an F-face scene), per-face lighting on the
+ * camera-space vertices n = normalize(cross(v0 - v1, v2 - v1), eps 1e-5), light = I_amb c_amb + I_dir c_dir relu(n . d), colour = face colour * light;
+ * projection x/(z+1e-9), y/(z+1e-9), K, v = orig_size - v, 2 (. - orig_size/2) / orig_size; vt_sil_forward's coverage rule (pixel centres, front faces,
+ * perspective-correct depth, 0.1 < z < 100, nearest face, ties to the smaller doubled id, row 0 = top); uncovered pixels = background, alpha 0, depth 100;
+ * anti_aliasing draws at 2 size and averages rgb, alpha and depth over 2 x 2 blocks.
+ *
+ * vt_render_rgb: verts (B,NV,3) camera coordinates, faces (NF,3) int32 and face_colors (NF,3) shared by the B views, K (B,9) (k_per_view != 0) or (9) shared,
+ *   orig_size (nr_utils.py:568-570: w * ratio); light = host {I_amb, I_dir, c_amb[3], c_dir[3], direction[3]} (11 floats; nr_utils.py:572-575:
+ *   0.4, 0.3, 1 1 1, 1 1 1, 1 0.5 1), background = host rgb[3].  static_layer: NULL, or a layer from vt_render_static_create built for the same K, orig_size,
+ *   light, size and anti_aliasing; the views then show the concatenated scene [mesh faces, layer faces] (nr_utils.py:801-808 add_checker), with doubled ids
+ *   numbered in that scene.  Outputs: rgb (B,size,size,3), alpha (B,size,size), depth (B,size,size) or NULL, face_index (B,is,is) int32 or NULL (owner's
+ *   doubled id, -1 = background; is = 2 size with anti-aliasing: the owners of the full-resolution raster).  ws: ws_bytes >= vt_render_workspace_bytes(B, NF,
+ *   size, anti_aliasing, L) bytes, where L is the batch's tile-list length.  The call synchronises `stream` once (after binning) to read L: it is written
+ *   to *list_entries (host, or NULL), and a workspace too small for it returns VT_ERR_ARG before anything is rasterised (grow it to L and call again).
+ * vt_render_static_create: a scene part shared by every view (render_recon.py:58-62, the xz ground checkerboard, already in camera coordinates: verts (NV,3),
+ *   faces (NS,3), face_colors (NS,3), K (9)), set up, binned and resolved once; owns its lit face records and a per-pixel depth / owner map (device memory,
+ *   allocated here; the temporary binning workspace is freed before it returns).  Synchronises `stream`.
+ * vt_render_panel_u8: (clip(rgb, 0, 1) * 255).astype(uint8) -- truncation -- of rows [row0, row0 + nrows) x columns [col0, col0 + ncols) of each (B,size,size,3)
+ *   view (render_side_comp.py:94, [:int(0.75 * 1200), 240:960]), written to out + view_off[b] (device int64 byte offsets) with out_row_stride bytes per row:
+ *   panels go straight into their place of the frame strip (render_recon.py:155-158). */
+long vt_render_workspace_bytes(int B, int NF, int size, int anti_aliasing, long list_entries);
+int vt_render_static_create(void **layer, const float *verts, int NV, const int *faces, int NS, const float *face_colors, const float *K, float orig_size,
+                            const float *light, int size, int anti_aliasing, void *stream);
+void vt_render_static_destroy(void *layer);
+int vt_render_rgb(const float *verts, int B, int NV, const int *faces, int NF, const float *face_colors, const float *K, int k_per_view, float orig_size,
+                  const float *light, const float *background, const void *static_layer, int size, int anti_aliasing, float *rgb, float *alpha, float *depth,
+                  int *face_index, void *ws, long ws_bytes, long *list_entries, void *stream);
+int vt_render_panel_u8(const float *rgb, int B, int size, int row0, int nrows, int col0, int ncols, unsigned char *out, const long long *view_off,
+                       long long out_row_stride, void *stream);
+
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two
  * workgroups of 256 threads per CU, non-trivial operands), out[1] = shader clock sustained during it (MHz: s_memtime against the 100 MHz s_memrealtime),

@@ -126,6 +126,12 @@ SIGNATURES = {
     "vt_fill": (ci, [fp, cl, cf, vp]),
     "vt_selftest_mfma": (ci, [fp, fp, fp, vp]),
     "vt_query_set_clock_probe": (ci, [vp]),
+    "vt_render_workspace_bytes": (cl, [ci, ci, ci, ci, cl]),
+    "vt_render_static_create": (ci, [C.POINTER(vp), fp, ci, fp, ci, fp, fp, cf, C.POINTER(cf), ci, ci, vp]),
+    "vt_render_static_destroy": (None, [vp]),
+    "vt_render_rgb": (ci, [fp, ci, ci, fp, ci, fp, fp, ci, cf, C.POINTER(cf), C.POINTER(cf), vp, ci, ci, fp, fp, fp, fp, fp, cl,
+                           C.POINTER(cl), vp]),
+    "vt_render_panel_u8": (ci, [fp, ci, ci, ci, ci, ci, ci, fp, fp, C.c_longlong, vp]),
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
 }

@@ -98,6 +98,18 @@ def resize_bilinear(img: np.ndarray, size: int) -> np.ndarray:
     return out
 
 
+def resize_bilinear_hw(img: np.ndarray, height: int, width: int) -> np.ndarray:
+    """cv2.resize(img, (width, height), INTER_LINEAR) for a non-square target (render/render_recon.py:157, the rgb panel of step 7: 1200 x 900);
+    the same arithmetic and uint8 rounding as ``resize_bilinear``."""
+    t = torch.as_tensor(np.ascontiguousarray(img), dtype=torch.float32)
+    t = t[None, None] if t.dim() == 2 else t.permute(2, 0, 1)[None]
+    out = torch.nn.functional.interpolate(t, size=(height, width), mode="bilinear", align_corners=False)[0]
+    out = (out[0] if img.ndim == 2 else out.permute(1, 2, 0)).numpy()
+    if np.asarray(img).dtype == np.uint8:
+        out = np.clip(np.floor(out + 0.5), 0, 255).astype(np.uint8)
+    return out
+
+
 # ---- A0: the batch dict of TestDataTriplane ------------------------------------------------------------------------------------------
 class SequenceLoader:
     """Iterable of batch dicts like ``TestDataTriplane(...).get_loader(shuffle=False)``: ``images (B,8,S,S)`` = RGB * (person | object), person

@@ -1,0 +1,508 @@
+"""Step 7 of the demo (scripts/demo.sh: render/render_side_comp.py): the fitted SMPL-H body and object, shaded, on a checkerboard ground, seen from
+two Kinect cameras next to the input image.
+
+Drop-ins for the reference's callables (render/nr_utils.py, render/checkerboard.py, render/render_recon.py, render/render_side_comp.py,
+behave/kinect_transform.py, behave/utils.py:41-70) with their signatures.  neural_renderer is replaced by the HIP rasteriser of
+``csrc/render.hip`` (``vt_render_rgb``; its rule is written down in that file's header): ``setup_renderer`` returns a parameter object in place of
+an ``nr.Renderer``.  The ground is rendered as a *static layer*: set up, binned and resolved once per camera, then the seed of every view's
+resolve (bit-identical to rendering the concatenated scene).  Not here: video encoding and ``cv2.putText`` labels (no cv2 / imageio), the
+``-add_top`` pytorch3d view, ``-w`` Procrustes alignment, PHOSA, contact spheres, lens distortion.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import os
+import os.path as osp
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import ops
+from .sequence_io import resize_bilinear_hw
+
+# render/nr_utils.py:282-296
+SMPL_OBJ_COLOR_LIST = [
+    [0.65098039, 0.74117647, 0.85882353],  # SMPL
+    [251 / 255.0, 128 / 255.0, 114 / 255.0],  # object
+]
+COLOR_LIST3 = [
+    [0.65098039, 0.74117647, 0.85882353],  # SMPL
+    [251 / 255.0, 128 / 255.0, 114 / 255.0],  # object
+    [23 / 255., 190 / 255., 207 / 255.],  # 3rd color
+]
+KINECT_SIZE = 2048.
+NEAR, FAR = 0.1, 100.0          # neural_renderer defaults; the kernel's clipping planes
+
+
+class Mesh:
+    """the part of psbody.mesh.Mesh step 7 uses: vertices ``v``, faces ``f``, face colours ``fc``"""
+
+    def __init__(self, v=None, f=None, fc=None):
+        self.v = None if v is None else np.asarray(v)
+        if f is not None:
+            self.f = np.asarray(f)
+        if fc is not None:
+            self.fc = np.asarray(fc)
+
+
+# ---- render/checkerboard.py ------------------------------------------------------------------------------------------------------------------
+class CheckerBoard:
+    def __init__(self, white=(247, 246, 244), black=(146, 163, 171)):
+        self.white = np.array(white) / 255.
+        self.black = np.array(black) / 255.
+        self.verts, self.faces, self.texts = None, None, None
+        self.offset = None
+        self.checker_mesh = None
+
+    def init_checker(self, offset, plane='xz', xlength=50, ylength=50, square_size=0.5):
+        """checkerboard.py:21-44: the xy board, rotated about x by 90 degrees for 'xz', then offset"""
+        checker = self.gen_checker_xy_no_repeat(self.black, self.white, square_size, xlength, ylength)
+        rot = np.eye(3)
+        if plane == 'xz':
+            rot[1, 1] = rot[2, 2] = 0
+            rot[1, 2] = -1
+            rot[2, 1] = 1
+        elif plane != 'xy':
+            raise NotImplementedError(plane)
+        checker.v = np.matmul(checker.v, rot.T)
+        self.checker_mesh = checker
+        checker.v += offset
+        self.offset = offset
+        self.verts, self.faces, self.texts = self.prep_checker_rend(checker)
+
+    def get_rends(self):
+        return self.verts, self.faces, self.texts
+
+    def append_checker(self, checker):
+        v, f, t = checker.get_rends()
+        nv = self.verts.shape[1]
+        self.verts = torch.cat([self.verts, v], 1)
+        self.faces = torch.cat([self.faces, f + nv], 1)
+        self.texts = torch.cat([self.texts, t], 1)
+
+    @staticmethod
+    def prep_checker_rend(checker: Mesh):
+        """(1,NV,3) float32, (1,NF,3) int64, (1,NF,1,1,1,3) float32 -- host tensors (the renderer uploads them once, as a static layer)"""
+        verts = torch.from_numpy(checker.v.astype(np.float32)).unsqueeze(0)
+        faces = torch.from_numpy(checker.f.astype(np.int64)).unsqueeze(0)
+        texts = torch.from_numpy(np.asarray(checker.fc, np.float32)).reshape(1, -1, 1, 1, 1, 3)
+        return verts, faces, texts
+
+    @staticmethod
+    def gen_checker_xy_no_repeat(black, white, square_size=0.5, xlength=5.0, ylength=5.0, vc=False):
+        """checkerboard.py:83-145: an xy board, normal +z, no repeated vertices; faces in the order of the reference's i (x) outer, j (y) inner
+        loops, two per square, squares with (i + j) even black"""
+        xsquares = int(xlength / square_size)
+        ysquares = int(ylength / square_size)
+        verts_count = (xsquares + 1) * (ysquares + 1)
+        x, y = np.arange(0, (xsquares + 1) * square_size, square_size), np.arange(0, (ysquares + 1) * square_size, square_size)
+        x, y = x[:xsquares + 1], y[:ysquares + 1]
+        xv, yv = np.meshgrid(x, y)
+        verts_all = np.stack((xv, yv, np.zeros_like(xv)), -1).reshape((verts_count, 3))
+        i, j = np.meshgrid(np.arange(xsquares), np.arange(ysquares), indexing="ij")
+        i, j = i.reshape(-1), j.reshape(-1)
+        w = xsquares + 1
+        f1 = np.stack([j * w + i, (j + 1) * w + i + 1, (j + 1) * w + i], -1)
+        f2 = np.stack([j * w + i, j * w + i + 1, (j + 1) * w + i + 1], -1)
+        faces = np.stack([f1, f2], 1).reshape(-1, 3)
+        col = np.where(((i + j) % 2 == 0)[:, None], np.asarray(black, np.float64)[None], np.asarray(white, np.float64)[None])
+        return Mesh(v=verts_all, f=faces, fc=np.repeat(col, 2, 0))
+
+
+# ---- render/nr_utils.py: cameras, scene layout -------------------------------------------------------------------------------------------------
+def get_intercap_K(image_size=1920, kid=0):
+    """nr_utils.py:480-497"""
+    ICAP_SIZE = 1920
+    assert kid in [0, 1, 2, 3, 4, 5], f'invalid kinect index {kid}!'
+    focals = np.array([[918.457763671875, 918.4373779296875], [915.29962158203125, 915.1966552734375],
+                       [912.8626708984375, 912.67633056640625], [909.82025146484375, 909.62469482421875],
+                       [920.533447265625, 920.09722900390625], [909.17633056640625, 909.23529052734375]])
+    centers = np.array([[956.9661865234375, 555.944580078125], [956.664306640625, 551.6165771484375],
+                        [956.72003173828125, 554.2166748046875], [957.6181640625, 554.60296630859375],
+                        [958.4615478515625, 550.42987060546875], [956.14801025390625, 555.01593017578125]])
+    fx, fy = focals[kid]
+    cx, cy = centers[kid]
+    ratio = image_size / ICAP_SIZE
+    return torch.tensor([[[fx * ratio, 0, cx * ratio], [0, fy * ratio, cy * ratio], [0, 0, 1]]], dtype=torch.float32), ratio
+
+
+def get_kinect_K(image_size=2048, kid=1):
+    """nr_utils.py:499-525"""
+    assert kid in [0, 1, 2, 3], f'invalid kinect index {kid}!'
+    fx, fy, cx, cy = {0: (976.212, 976.047, 1017.958, 787.313), 1: (979.784, 979.840, 1018.952, 779.486),
+                      2: (974.899, 974.337, 1018.747, 786.176), 3: (972.873, 972.790, 1022.0565, 770.397)}[kid]
+    ratio = image_size / KINECT_SIZE
+    return torch.tensor([[[fx * ratio, 0, cx * ratio], [0, fy * ratio, cy * ratio], [0, 0, 1]]], dtype=torch.float32), ratio
+
+
+class RenderParams(SimpleNamespace):
+    """what nr.Renderer(image_size, K, R, t, orig_size) holds after setup_renderer (nr_utils.py:567-577) plus neural_renderer's defaults"""
+
+    def light(self) -> np.ndarray:
+        return np.array([self.light_intensity_ambient, self.light_intensity_direction, *self.light_color_ambient, *self.light_color_directional,
+                         *self.light_direction], np.float32)
+
+    def key(self):
+        return (self.image_size, bool(self.anti_aliasing), float(self.orig_size), self.K.numpy().tobytes(), self.R.numpy().tobytes(),
+                self.t.numpy().tobytes(), self.light().tobytes())
+
+
+def setup_renderer(view='front', rotate=False, image_size=2048, kid=1, distort=False, dataset_name='behave', R=None, T=None):
+    """nr_utils.py:534-577 -> RenderParams (light [1, 0.5, 1], directional 0.3, ambient 0.4, white background, anti-aliasing, fill_back)"""
+    assert dataset_name in ['behave', 'InterCap']
+    if distort:
+        raise NotImplementedError("lens distortion is not part of step 7 (every call of the demo passes distort=False)")
+    w, func = (2048, get_kinect_K) if dataset_name == 'behave' else (1920, get_intercap_K)
+    K, ratio = func(image_size, kid)
+    if R is None:
+        if view == 'front':
+            R = torch.tensor([[[-1., 0, 0], [0, -1, 0], [0, 0, 1]]] if rotate else [[[1., 0, 0], [0, 1, 0], [0, 0, 1]]])
+            t = torch.zeros(1, 3)
+        elif view == 'top':
+            theta, d = 1.3, 1.3
+            x, y = np.cos(theta), np.sin(theta)
+            R = torch.tensor([[[1, 0, 0], [0, x, -y], [0, y, x]]], dtype=torch.float32)
+            t = torch.tensor([0., 0. + d, 2.5])
+        else:
+            raise NotImplementedError(view)
+    else:
+        t = T
+    return RenderParams(image_size=image_size, K=K, R=torch.as_tensor(R, dtype=torch.float32).reshape(1, 3, 3).cpu(),
+                        t=torch.as_tensor(t, dtype=torch.float32).reshape(1, 3).cpu(), orig_size=w * ratio,
+                        light_direction=[1, 0.5, 1], light_intensity_direction=0.3, light_intensity_ambient=0.4,
+                        light_color_ambient=[1, 1, 1], light_color_directional=[1, 1, 1], background_color=[1, 1, 1],
+                        anti_aliasing=True, fill_back=True, near=NEAR, far=FAR)
+
+
+def get_faces_and_textures(verts_list, faces_list, colors_list=SMPL_OBJ_COLOR_LIST):
+    """nr_utils.py:381-415: faces (1,F,3) with per-mesh vertex offsets, one colour per face (1,F,1,1,1,3)"""
+    all_faces, all_tex = [], []
+    o = 0
+    for verts, faces, colors in zip(verts_list, faces_list, colors_list):
+        B = len(verts)
+        index_offset = torch.arange(B).to(verts.device) * verts.shape[1] + o
+        o += verts.shape[1] * B
+        faces_repeat = faces.clone().repeat(B, 1, 1)
+        faces_repeat += index_offset.view(-1, 1, 1)
+        faces_repeat = faces_repeat.reshape(-1, 3)
+        all_faces.append(faces_repeat)
+        all_tex.append(torch.tensor(colors, dtype=torch.float32, device=verts.device).repeat(faces_repeat.shape[0], 1, 1, 1, 1))
+    return torch.cat(all_faces).unsqueeze(0), torch.cat(all_tex).unsqueeze(0)
+
+
+# ---- the rasteriser ------------------------------------------------------------------------------------------------------------------------
+class StaticLayer:
+    """vt_render_static_create: a part of the scene shared by every view of one camera (verts already in its coordinates)"""
+
+    def __init__(self, verts, faces, colors, params: RenderParams, device="cuda:0"):
+        dev = torch.device(device)
+        self.params_key, self.NS = params.key(), int(faces.shape[0])
+        v = torch.as_tensor(verts, dtype=torch.float32).reshape(-1, 3).to(dev)
+        v = (v @ params.R[0].to(dev).T + params.t[0].to(dev)).contiguous()
+        f = torch.as_tensor(np.asarray(faces), dtype=torch.int32).reshape(-1, 3).to(dev).contiguous()
+        c = torch.as_tensor(np.asarray(colors), dtype=torch.float32).reshape(-1, 3).to(dev).contiguous()
+        K = params.K.reshape(9).to(dev).contiguous()
+        light = params.light()
+        h = C.c_void_p()
+        with torch.cuda.device(dev):
+            L.check(L.lib().vt_render_static_create(C.byref(h), L.dptr(v), v.shape[0], L.dptr(f), self.NS, L.dptr(c), L.dptr(K), float(params.orig_size),
+                                                    light.ctypes.data_as(C.POINTER(C.c_float)), int(params.image_size), int(bool(params.anti_aliasing)),
+                                                    L.stream_ptr()))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                L.lib().vt_render_static_destroy(self.h)
+        except Exception:
+            pass
+
+
+class ShadedRasterizer:
+    """vt_render_rgb with a cached workspace that grows to the largest tile list seen"""
+
+    def __init__(self, device="cuda:0"):
+        self.device = torch.device(device)
+        self.ws = None
+        self.entries = 0
+        self.last_entries = 0
+
+    def render(self, verts, faces, colors, params: RenderParams, static: StaticLayer | None = None, K=None, want_depth=False, want_index=False):
+        """verts (B,NV,3) world-of-the-renderer coordinates (R, t of ``params`` are applied here), faces (NF,3), colors (NF,3) -> dict of
+        rgb (B,S,S,3), alpha (B,S,S), depth, face_index (device tensors)"""
+        if not params.fill_back or params.near != NEAR or params.far != FAR:
+            raise NotImplementedError("the rasteriser implements neural_renderer's defaults: fill_back, near 0.1, far 100")
+        dev = self.device
+        v = torch.as_tensor(verts, dtype=torch.float32, device=dev)
+        if not (torch.equal(params.R[0], torch.eye(3)) and not params.t.any()):
+            v = v @ params.R[0].to(dev).T + params.t[0].to(dev)
+        v = v.contiguous()
+        B, NV = v.shape[0], v.shape[1]
+        f = torch.as_tensor(faces, dtype=torch.int32, device=dev).reshape(-1, 3).contiguous()
+        c = torch.as_tensor(colors, dtype=torch.float32, device=dev).reshape(-1, 3).contiguous()
+        NF = f.shape[0]
+        size, aa = int(params.image_size), int(bool(params.anti_aliasing))
+        if static is not None and static.params_key != params.key():
+            raise ValueError("static layer was built for another camera / size / light")
+        if K is None:
+            Kd, kpv = params.K.reshape(9).to(dev).contiguous(), 0
+        else:
+            Kd, kpv = torch.as_tensor(K, dtype=torch.float32, device=dev).reshape(B, 9).contiguous(), 1
+        rs = size * (2 if aa else 1)
+        rgb = torch.empty(B, size, size, 3, device=dev); alpha = torch.empty(B, size, size, device=dev)
+        depth = torch.empty(B, size, size, device=dev) if want_depth else None
+        fidx = torch.empty(B, rs, rs, dtype=torch.int32, device=dev) if want_index else None
+        light = params.light(); bg = np.asarray(params.background_color, np.float32)
+        need = C.c_long(0)
+        want = max(self.entries, 2 * B * NF + B * (rs // 16) ** 2)
+        for _ in range(2):
+            nbytes = L.lib().vt_render_workspace_bytes(B, NF, size, aa, want)
+            if self.ws is None or self.ws.numel() < nbytes:
+                self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            rc = L.lib().vt_render_rgb(L.dptr(v), B, NV, L.dptr(f), NF, L.dptr(c), L.dptr(Kd), kpv, float(params.orig_size),
+                                       light.ctypes.data_as(C.POINTER(C.c_float)), bg.ctypes.data_as(C.POINTER(C.c_float)),
+                                       static.h if static is not None else None, size, aa, L.dptr(rgb), L.dptr(alpha), L.dptr(depth), L.dptr(fidx),
+                                       L.dptr(self.ws), self.ws.numel(), C.byref(need), L.stream_ptr())
+            if rc == 0 or need.value <= want:
+                break
+            want = int(need.value * 1.25) + 1024                            # the list did not fit: grow to it and render again
+        L.check(rc)
+        self.last_entries = need.value
+        self.entries = max(self.entries, want)
+        return {"rgb": rgb, "alpha": alpha, "depth": depth, "face_index": fidx}
+
+
+def panels_u8(rgb, out, view_off, row0, nrows, col0, ncols, row_stride):
+    """vt_render_panel_u8: (clip(rgb, 0, 1) * 255).astype(uint8) crops of (B,S,S,3) renders into the uint8 tensor ``out`` at byte offsets view_off (B,)"""
+    B, S = rgb.shape[0], rgb.shape[1]
+    off = torch.as_tensor(view_off, dtype=torch.int64, device=rgb.device).contiguous()
+    L.check(L.lib().vt_render_panel_u8(L.dptr(rgb.contiguous()), B, S, row0, nrows, col0, ncols, out.data_ptr(), L.dptr(off), row_stride, L.stream_ptr()))
+
+
+class NrWrapper:
+    """nr_utils.py:663-808 (the camera-view path)"""
+
+    def __init__(self, device='cuda:0', image_size=1024, colors=None, contact_viz_type='sphere', dataset_name='behave', kid=1):
+        self.device = device
+        self.colors = [list(c) for c in SMPL_OBJ_COLOR_LIST] if colors is None else colors
+        self.smpl_color, self.obj_color = SMPL_OBJ_COLOR_LIST[0], SMPL_OBJ_COLOR_LIST[1]
+        self.front_renderer = setup_renderer(image_size=image_size, dataset_name=dataset_name, kid=kid)
+        self.image_size = image_size
+        self.contact_viz_type = contact_viz_type
+        self.raster = ShadedRasterizer(device)
+        self._layers = {}
+
+    def static_layer(self, renderer: RenderParams, checker: CheckerBoard) -> StaticLayer:
+        """the checker of ``renderer`` as a static layer, built once per (checker, camera)"""
+        key = (id(checker), renderer.key())
+        if key not in self._layers:
+            cv, cf, ct = checker.get_rends()
+            self._layers[key] = (checker, StaticLayer(cv[0], cf[0], ct.reshape(-1, 3), renderer, self.device))
+        return self._layers[key][1]
+
+    def prepare_render(self, meshes, viz_contact=False, colors=None, checker=None, radius=None):
+        """nr_utils.py:760-799 without contact spheres: verts (1,NV,3), faces (1,F,3), textures (1,F,1,1,1,3), ground appended last"""
+        if viz_contact:
+            raise NotImplementedError("contact spheres are not part of step 7")
+        render_color = self.colors if colors is None else colors
+        verts_list = [torch.as_tensor(np.asarray(m.v), dtype=torch.float32).unsqueeze(0) for m in meshes]
+        faces_list = [torch.as_tensor(np.asarray(m.f).astype(np.int32)) for m in meshes]
+        faces, textures = get_faces_and_textures(verts_list, faces_list, colors_list=list(render_color)[:len(meshes)])
+        verts = torch.cat(verts_list, 1)
+        if checker is not None:
+            cv, cf, ct = checker.get_rends()
+            faces = torch.cat([faces, verts.shape[1] + cf.to(faces.dtype)], 1)
+            textures = torch.cat([textures, ct], 1)
+            verts = torch.cat([verts, cv], 1)
+        return verts, faces, textures
+
+    def render_meshes(self, renderer, meshes: list, viz_contact=False, ret_depth=False, checker=None, colors=None):
+        """-> rend (H,W,3) float32 in [0, 1], mask (H,W) bool (and depth): NrWrapper.render of the meshes, checker as a static layer"""
+        verts, faces, textures = self.prepare_render(meshes, viz_contact, colors=colors)
+        layer = self.static_layer(renderer, checker) if checker is not None else None
+        out = self.raster.render(verts, faces[0], textures.reshape(-1, 3), renderer, static=layer, want_depth=ret_depth)
+        rend = np.clip(out["rgb"][0].cpu().numpy(), 0, 1)
+        mask = out["alpha"][0].cpu().numpy().astype(bool)
+        if ret_depth:
+            return rend, mask, out["depth"][0].cpu().numpy()
+        return rend, mask
+
+
+# ---- behave/utils.py:41-70, behave/kinect_transform.py -------------------------------------------------------------------------------------------
+def load_kinect_poses(config_folder, kids):
+    pose_calibs = [json.load(open(osp.join(config_folder, f"{x}/config.json"))) for x in kids]
+    rotations = [np.array(pose_calibs[x]['rotation']).reshape((3, 3)) for x in range(len(kids))]
+    translations = [np.array(pose_calibs[x]['translation']) for x in range(len(kids))]
+    return rotations, translations
+
+
+def load_kinect_poses_back(config_folder, kids, rotate=False):
+    """world (camera 1 colour frame) -> camera k: the inverse of each {k}/config.json pose"""
+    rotations, translations = load_kinect_poses(config_folder, kids)
+    rb, tb = [], []
+    for r, t in zip(rotations, translations):
+        trans = np.eye(4)
+        trans[:3, :3] = r
+        trans[:3, 3] = t
+        back = np.linalg.inv(trans)
+        r_back, t_back = back[:3, :3], back[:3, 3]
+        if rotate:
+            g = np.eye(4); g[0, 0] = g[1, 1] = -1
+            rot = np.matmul(g, np.concatenate([np.concatenate([r_back, t_back[:, None]], 1), [[0, 0, 0, 1]]], 0))
+            r_back, t_back = rot[:3, :3], rot[:3, 3]
+        rb.append(r_back)
+        tb.append(t_back)
+    return rb, tb
+
+
+def seq_config_folder(seq):
+    """behave/seq_utils.py:48-60: the 'config' entry of <seq>/info.json, relative to the sequence unless that is no folder"""
+    info = json.load(open(osp.join(seq, 'info.json')))
+    path = osp.join(seq, info['config'])
+    kids = list(range(len(info['kinects']) if 'kinects' in info else 3))
+    return (path if osp.isdir(path) else info['config']), kids
+
+
+class KinectTransform:
+    """world (camera 1 colour frame) <-> camera k.  ``KinectTransform(seq)`` reads the sequence's config folder like the reference (intrinsics are not
+    loaded: step 7 passes no_intrinsic=True); ``KinectTransform(world2local_R=[...], world2local_t=[...])`` takes the per-camera arrays directly."""
+
+    def __init__(self, seq=None, kinect_count=4, no_intrinsic=True, world2local_R=None, world2local_t=None):
+        if not no_intrinsic:
+            raise NotImplementedError("Kinect intrinsics (behave/kinect_calib.py) are not needed by step 7")
+        self.intrinsics = None
+        if seq is not None:
+            config, self.kids = seq_config_folder(seq)
+            self.local2world_R, self.local2world_t = load_kinect_poses(config, self.kids)
+            self.world2local_R, self.world2local_t = load_kinect_poses_back(config, self.kids)
+        else:
+            self.world2local_R = [np.asarray(r, np.float64).reshape(3, 3) for r in world2local_R]
+            self.world2local_t = [np.asarray(t, np.float64).reshape(3) for t in world2local_t]
+            self.kids = list(range(len(self.world2local_R)))
+            inv = [np.linalg.inv(np.concatenate([np.concatenate([r, t[:, None]], 1), [[0, 0, 0, 1]]], 0)) for r, t in zip(self.world2local_R, self.world2local_t)]
+            self.local2world_R, self.local2world_t = [m[:3, :3] for m in inv], [m[:3, 3] for m in inv]
+
+    def world2local(self, points, kid):
+        return np.matmul(points, self.world2local_R[kid].T) + self.world2local_t[kid]
+
+    def local2world(self, points, kid):
+        return np.matmul(points, self.local2world_R[kid].T) + self.local2world_t[kid]
+
+    def world2color_mesh(self, mesh, kid):
+        m = Mesh(v=self.world2local(mesh.v, kid), f=getattr(mesh, 'f', None))
+        return m
+
+    def world2local_meshes(self, meshes, kid):
+        return [self.world2color_mesh(m, kid) for m in meshes]
+
+    def world2local_torch(self, verts, kid):
+        """device version for batches: verts (..., 3) tensor"""
+        R = torch.as_tensor(self.world2local_R[kid], dtype=torch.float32, device=verts.device)
+        t = torch.as_tensor(self.world2local_t[kid], dtype=torch.float32, device=verts.device)
+        return verts @ R.T + t
+
+
+def object_verts(temp_v, obj_angles, obj_trans, obj_scales):
+    """render_recon.py:323-324 (prepare_verts): (temp.v @ obj_angles + obj_trans) * obj_scales, numpy in, numpy out (float64 like the reference)"""
+    v = np.matmul(np.asarray(temp_v)[None], np.asarray(obj_angles)) + np.asarray(obj_trans)[:, None]
+    return v * np.asarray(obj_scales).reshape(-1, 1, 1)
+
+
+# ---- render/render_side_comp.py + render_recon.py:render_seq ---------------------------------------------------------------------------------
+class RendererSide2side:
+    """Side-by-side frames: [input rgb | camera kid recon_1 .. recon_n | camera kid + 1 recon_1 .. recon_n], each panel the rows [:0.75 size] and
+    columns [0.2 size, 0.8 size) of a size x size render (render_side_comp.py:71-98, render_recon.py:41-160).  Camera 1's intrinsics render every
+    view (the reference's single front renderer, NrWrapper(kid=1))."""
+
+    def __init__(self, image_size=1200, gender='male', dataset_name='behave', kid=None, device='cuda:0', xcut_start=0.2, xcut_end=0.8):
+        self.test_id = (1 if dataset_name == 'behave' else 0) if kid is None else kid
+        self.aspect_ratio = 0.75 if dataset_name == 'behave' else 9 / 16.
+        self.nrwrapper = NrWrapper(image_size=image_size, colors=COLOR_LIST3, dataset_name=dataset_name, device=device)
+        checker_xz = CheckerBoard()
+        psize = 80.0
+        checker_xz.init_checker(np.array([-psize / 2., 1.5, -psize / 2.]), 'xz', square_size=0.5, xlength=psize, ylength=psize)
+        self.ground_xz = checker_xz
+        self.image_size, self.device = image_size, device
+        self.xcut_start, self.xcut_end = xcut_start, xcut_end
+
+    def get_xcuts(self, image_size):
+        return int(self.xcut_start * image_size), int(self.xcut_end * image_size)
+
+    def frame_shape(self, n_recons):
+        cs, ce = self.get_xcuts(self.image_size)
+        return int(self.aspect_ratio * self.image_size), (ce - cs) * (1 + 2 * n_recons), 3
+
+    def render_frames(self, recons, temp_v, temp_f, smpl_handle, kin, rgb=None, start=0, end=None, interval=1, chunk=8):
+        """Generator of uint8 frame chunks (n, H, W, 3) for frames start:end:interval of the packed ``recons`` (dicts with poses (T,156), betas,
+        trans, obj_angles (T,3,3), obj_trans, obj_scales).  ``smpl_handle``: ops.SmplhHandle of the sequence's SMPL-H model; ``kin``: KinectTransform;
+        ``rgb``: None (black panel), a sequence or a callable frame index -> (h,w,3) uint8 image of camera test_id.  Every chunk renders
+        chunk x 2 x len(recons) views in one vt_render_rgb call, the ground as one static layer."""
+        dev = torch.device(self.device)
+        size = self.image_size
+        cs, ce = self.get_xcuts(size)
+        H, W, _ = self.frame_shape(len(recons))
+        pw = ce - cs
+        n = len(recons)
+        T = len(recons[0]["poses"])
+        end = T if end is None else end
+        frames = list(range(start, end, interval))
+        renderer = self.nrwrapper.front_renderer
+        layer = self.nrwrapper.static_layer(renderer, self.ground_xz)
+        temp_f = np.asarray(temp_f)
+        smpl_f = np.asarray(smpl_handle.faces)
+        nvs = 6890
+        faces = np.concatenate([smpl_f, temp_f + nvs], 0).astype(np.int32)
+        colors = np.concatenate([np.tile(np.asarray(self.nrwrapper.colors[0], np.float32), (len(smpl_f), 1)),
+                                 np.tile(np.asarray(self.nrwrapper.colors[1], np.float32), (len(temp_f), 1))], 0)
+        faces_d = torch.as_tensor(faces, device=dev); colors_d = torch.as_tensor(colors, device=dev)
+        tv = torch.as_tensor(np.asarray(temp_v), dtype=torch.float32, device=dev)
+        kids = [self.test_id, self.test_id + 1]
+        with torch.cuda.device(dev):
+            for c0 in range(0, len(frames), chunk):
+                idx = frames[c0:c0 + chunk]
+                nc = len(idx)
+                ii = torch.as_tensor(idx, device=dev)
+                per_recon = []
+                for d in recons:
+                    g = lambda k, w: torch.as_tensor(np.asarray(d[k], np.float32).reshape(T, w), device=dev)[ii].contiguous()
+                    sv, _, _ = ops.smplh_forward(smpl_handle, g("poses", 156), g("betas", 10), g("trans", 3))
+                    R = g("obj_angles", 9).reshape(nc, 3, 3); t = g("obj_trans", 3); s = g("obj_scales", 1)
+                    ov = (tv[None] @ R + t[:, None]) * s[:, :, None]
+                    per_recon.append(torch.cat([sv.detach(), ov], 1))
+                views = torch.stack([torch.stack([kin.world2local_torch(v, k) for v in per_recon], 1) for k in kids], 1)   # (nc, 2, n, NV, 3)
+                views = views.reshape(nc * 2 * n, views.shape[-2], 3).contiguous()
+                if bool((views[..., 2].amin() < 0).item()):
+                    raise ValueError("a mesh lies behind the camera (render_side_comp.py:86-90 allows that for PHOSA only)")
+                out = self.nrwrapper.raster.render(views, faces_d, colors_d, renderer, static=layer)
+                buf = torch.zeros(nc, H, W, 3, dtype=torch.uint8, device=dev)
+                b = torch.arange(nc * 2 * n, device=dev)
+                off = (b // (2 * n)) * (H * W * 3) + (1 + b % (2 * n)) * (pw * 3)
+                panels_u8(out["rgb"], buf, off, 0, H, cs, pw, W * 3)
+                if rgb is not None:
+                    for j, i in enumerate(idx):
+                        img = rgb(i) if callable(rgb) else rgb[i]
+                        img = resize_bilinear_hw(np.asarray(img), H, size)[:, cs:ce]
+                        buf[j, :, :pw] = torch.as_tensor(np.ascontiguousarray(img), device=dev)
+                yield buf.cpu().numpy()
+
+
+def write_frames(frames, outdir, start=0, prefix="frame"):
+    """Write frames (an iterable of (H,W,3) uint8 frames or of (n,H,W,3) chunks) as PNG through PIL, or .npy where PIL is absent.  Returns the paths."""
+    os.makedirs(outdir, exist_ok=True)
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    paths, k = [], start
+    for ch in frames:
+        ch = np.asarray(ch)
+        for fr in (ch if ch.ndim == 4 else ch[None]):
+            if Image is not None:
+                p = osp.join(outdir, f"{prefix}_{k:05d}.png"); Image.fromarray(fr).save(p)
+            else:
+                p = osp.join(outdir, f"{prefix}_{k:05d}.npy"); np.save(p, fr)
+            paths.append(p); k += 1
+    return paths
