@@ -545,6 +545,23 @@ int vt_render_rgb(const float *verts, int B, int NV, const int *faces, int NF, c
 int vt_render_panel_u8(const float *rgb, int B, int size, int row0, int nrows, int col0, int ncols, unsigned char *out, const long long *view_off,
                        long long out_row_stride, void *stream);
 
+/* ---- Motion-JPEG video of demo step 7 (render/render_side_comp.py:71-72 drives render/render_recon.py, which appends every frame to an imageio FFMPEG
+ * writer: render_recon.py:113-115 imageio.get_writer(..., format='FFMPEG', fps), :169 and :188 writer.append_data(frame)) --------------------------------
+ * Baseline sequential JPEG of uint8 RGB frames already in device memory; the contract (JFIF BT.601 colour in fp32, 4:2:0 = mean of 2 x 2 or 4:4:4,
+ * orthonormal fp32 DCT, IJG quality tables, Annex K Huffman tables, restart interval of one MCU row) is written in jpeg.hip's header and restated in float64 by
+ * tests/jpeg_model.py.  vistracker_amd/video.py builds the per-size header (SOI .. SOS) and the AVI file.
+ *
+ * vt_jpeg_workspace_bytes: device workspace bytes of a call on n frames of H x W (subsampling 420 or 444), -1 on bad sizes; *max_out_bytes (host, or NULL)
+ *   receives the worst case of the call's output (1660 bits per block before stuffing, stuffing doubling, two marker bytes per MCU row).
+ * vt_jpeg_encode: frame f at rgb + f * frame_stride (bytes), rows row_stride bytes apart (>= 3 W), pixels packed: a (n,H,W,3) tensor or a strided view of one
+ *   with packed pixels.  quality 1..100.  Writes, per frame, the entropy-coded data that follows SOS (segments separated by RSTm markers, EOI at the end)
+ *   into the HOST buffer out, frames back to back: frame f is out[offsets[f], offsets[f + 1]) (offsets: host, n + 1 entries).  out_cap must hold the worst
+ *   case (*max_out_bytes) and ws_bytes the workspace: both are checked before anything is launched (VT_ERR_ARG, the needed size in the message).  The call
+ *   synchronises `stream`: once to read the n + 1 offsets, once after the one device-to-host copy of exactly the used bytes. */
+long vt_jpeg_workspace_bytes(int n, int H, int W, int subsampling, long long *max_out_bytes);
+int vt_jpeg_encode(const unsigned char *rgb, int n, int H, int W, long long frame_stride, long long row_stride, int quality, int subsampling, void *ws,
+                   long ws_bytes, unsigned char *out, long long out_cap, long long *offsets, void *stream);
+
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two
  * workgroups of 256 threads per CU, non-trivial operands), out[1] = shader clock sustained during it (MHz: s_memtime against the 100 MHz s_memrealtime),

@@ -132,6 +132,9 @@ SIGNATURES = {
     "vt_render_rgb": (ci, [fp, ci, ci, fp, ci, fp, fp, ci, cf, C.POINTER(cf), C.POINTER(cf), vp, ci, ci, fp, fp, fp, fp, fp, cl,
                            C.POINTER(cl), vp]),
     "vt_render_panel_u8": (ci, [fp, ci, ci, ci, ci, ci, ci, fp, fp, C.c_longlong, vp]),
+    "vt_jpeg_workspace_bytes": (cl, [ci, ci, ci, ci, C.POINTER(C.c_longlong)]),
+    "vt_jpeg_encode": (ci, [fp, ci, ci, ci, C.c_longlong, C.c_longlong, ci, ci, vp, cl, vp, C.c_longlong,
+                            C.POINTER(C.c_longlong), vp]),
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
 }

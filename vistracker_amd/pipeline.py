@@ -340,14 +340,22 @@ class SequencePipeline:
         lap("6_joint_fit")
         return out
 
-    def render(self, out, kin, rgb=None, template=None, outdir=None, start=0, end=None, interval=1, chunk=8, image_size=1200):
+    def render(self, out, kin, rgb=None, template=None, outdir=None, start=0, end=None, interval=1, chunk=8, image_size=1200,
+               video=None, fps=30, quality=90):
         """demo step 7 (render/render_side_comp.py -s1 <recon>) on ``out["recon"]`` of ``run``: side-by-side frames [input rgb | camera 1 | camera 2]
         of the fitted SMPL-H body and object on the checkerboard ground (visualize.RendererSide2side).  ``kin``: visualize.KinectTransform of the
         sequence; ``template``: (verts, faces) of the object template; ``rgb``: None, a sequence or a callable frame index -> camera-1 image.  With
-        ``outdir`` the frames are written there (PNG) and their paths returned, otherwise the generator of uint8 frame chunks is."""
+        ``outdir`` the frames are written there (PNG) and their paths returned; with ``video`` (a path) they go, without leaving the device, into a
+        Motion-JPEG AVI at ``fps`` (render_recon.py -fps, 30) and JPEG ``quality`` (video.write_video) and the path is returned; otherwise the
+        generator of uint8 frame chunks is."""
         from . import visualize
         if template is None:
             raise ValueError("render() needs the object template (verts, faces)")
         r = visualize.RendererSide2side(image_size=image_size, device=self.device)
+        if video is not None:
+            from . import video as vid
+            gen = r.render_frames([out["recon"]], template[0], template[1], self.ctx.smpl, kin, rgb=rgb, start=start, end=end, interval=interval, chunk=chunk,
+                                  on_device=True)
+            return vid.write_video(gen, video, fps=fps, quality=quality)[0]
         gen = r.render_frames([out["recon"]], template[0], template[1], self.ctx.smpl, kin, rgb=rgb, start=start, end=end, interval=interval, chunk=chunk)
         return visualize.write_frames(gen, outdir, start=start) if outdir is not None else gen

@@ -5,8 +5,9 @@ Drop-ins for the reference's callables (render/nr_utils.py, render/checkerboard.
 behave/kinect_transform.py, behave/utils.py:41-70) with their signatures.  neural_renderer is replaced by the HIP rasteriser of
 ``csrc/render.hip`` (``vt_render_rgb``; its rule is written down in that file's header): ``setup_renderer`` returns a parameter object in place of
 an ``nr.Renderer``.  The ground is rendered as a *static layer*: set up, binned and resolved once per camera, then the seed of every view's
-resolve (bit-identical to rendering the concatenated scene).  Not here: video encoding and ``cv2.putText`` labels (no cv2 / imageio), the
-``-add_top`` pytorch3d view, ``-w`` Procrustes alignment, PHOSA, contact spheres, lens distortion.
+resolve (bit-identical to rendering the concatenated scene).  The video is ``video.write_video`` (Motion-JPEG AVI, GPU JPEG encoder; frames from
+``render_frames(..., on_device=True)`` never leave the device).  Not here: ``cv2.putText`` labels (no cv2), the ``-add_top`` pytorch3d view,
+``-w`` Procrustes alignment, PHOSA, contact spheres, lens distortion.
 """
 from __future__ import annotations
 
@@ -435,11 +436,12 @@ class RendererSide2side:
         cs, ce = self.get_xcuts(self.image_size)
         return int(self.aspect_ratio * self.image_size), (ce - cs) * (1 + 2 * n_recons), 3
 
-    def render_frames(self, recons, temp_v, temp_f, smpl_handle, kin, rgb=None, start=0, end=None, interval=1, chunk=8):
+    def render_frames(self, recons, temp_v, temp_f, smpl_handle, kin, rgb=None, start=0, end=None, interval=1, chunk=8, on_device=False):
         """Generator of uint8 frame chunks (n, H, W, 3) for frames start:end:interval of the packed ``recons`` (dicts with poses (T,156), betas,
         trans, obj_angles (T,3,3), obj_trans, obj_scales).  ``smpl_handle``: ops.SmplhHandle of the sequence's SMPL-H model; ``kin``: KinectTransform;
         ``rgb``: None (black panel), a sequence or a callable frame index -> (h,w,3) uint8 image of camera test_id.  Every chunk renders
-        chunk x 2 x len(recons) views in one vt_render_rgb call, the ground as one static layer."""
+        chunk x 2 x len(recons) views in one vt_render_rgb call, the ground as one static layer.  ``on_device=True`` yields the chunks as uint8 device
+        tensors (for ``video.write_video``) instead of host arrays."""
         dev = torch.device(self.device)
         size = self.image_size
         cs, ce = self.get_xcuts(size)
@@ -486,7 +488,7 @@ class RendererSide2side:
                         img = rgb(i) if callable(rgb) else rgb[i]
                         img = resize_bilinear_hw(np.asarray(img), H, size)[:, cs:ce]
                         buf[j, :, :pw] = torch.as_tensor(np.ascontiguousarray(img), device=dev)
-                yield buf.cpu().numpy()
+                yield buf if on_device else buf.cpu().numpy()
 
 
 def write_frames(frames, outdir, start=0, prefix="frame"):
