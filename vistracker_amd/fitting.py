@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import functools
 import os
 import threading
 import time
@@ -93,7 +94,8 @@ class Terms:
 
 
 class AdamState:
-    """torch.optim.Adam over column slices of parameter tensors (one launch per slice)."""
+    """torch.optim.Adam over column slices of parameter tensors: one launch per slice (``step``), or the groups handed to the tail of a fused step
+    (``tick`` + ``smpl_tail_groups`` / ``object_tail_groups``)."""
 
     def __init__(self, slices, stop_flag):
         # slices: list of (tensor (B, C) contiguous, ncols, grad tensor (B, Cg) contiguous, lr)
@@ -103,11 +105,36 @@ class AdamState:
         self.t = 0
         self.stop_flag = stop_flag
 
-    def step(self):
+    def tick(self):
+        """the step counter of the next Adam step"""
         self.t += 1
+        return self.t
+
+    def step(self):
+        t = self.tick()
         for (p, n, g, lr), m, v in zip(self.slices, self.m, self.v):
             _chk(_lib().vt_adam_step_2d(p.data_ptr(), p.shape[1], g.data_ptr(), g.shape[1], m.data_ptr(), v.data_ptr(), p.shape[0], n,
-                                        self.t, lr, 0.9, 0.999, 1e-8, self.stop_flag.data_ptr(), L.stream_ptr()))
+                                        t, lr, 0.9, 0.999, 1e-8, self.stop_flag.data_ptr(), L.stream_ptr()))
+
+    # the pointers of the groups never change: the fused tails' argument lists are packed once per AdamState
+    @functools.cached_property
+    def smpl_tail_groups(self):
+        """vt_smplstep_tail's three groups (param, stride, grad, stride, m, v, ncols, lr); unused ones NULL"""
+        out = ()
+        for (p, n, g, lr), m, v in zip(self.slices, self.m, self.v):
+            out += (p.data_ptr(), p.shape[1], g.data_ptr(), g.shape[1], m.data_ptr(), v.data_ptr(), n, lr)
+        return out + (None, 0, None, 0, None, None, 0, 0.0) * (3 - len(self.slices))
+
+    @functools.cached_property
+    def object_tail_groups(self):
+        """vt_objstep_tail's (param, m, v, lr) of the rotation group (9 columns), then of the translation group; a group not optimised is NULL"""
+        rot = trans = (None, None, None, 0.0)
+        for (p, n, g, lr), m, v in zip(self.slices, self.m, self.v):
+            if n == 9:
+                rot = (p.data_ptr(), m.data_ptr(), v.data_ptr(), lr)
+            else:
+                trans = (p.data_ptr(), m.data_ptr(), v.data_ptr(), lr)
+        return rot + trans
 
 
 def _check_finite(res, what):
@@ -172,9 +199,11 @@ def morton_order_device(p: torch.Tensor) -> torch.Tensor:
 
 
 class _StopWatch:
-    """FitContext._stop_watch: the device-side stop flag as the launching thread sees it.  Without look-ahead ``check()`` is a stream synchronisation (the
-    flag of the iteration just queued).  With it, ``check()`` queues an asynchronous copy of the flag to pinned memory and an event behind the iteration
-    just queued and waits for the PREVIOUS iteration's event: one iteration of launches always stands between the host and the GPU."""
+    """The device-side stop flag of one fit as the launching thread sees it, once per outer iteration.  With the look-ahead (``lookahead``: the fit has the
+    device-side skip, see FitContext._skip_after_stop) ``check()`` queues an asynchronous copy of the flag to pinned memory and an event behind the iteration
+    just queued and waits for the PREVIOUS iteration's event: one iteration of launches always stands between the host and the GPU, so the stream never runs
+    dry while the launching thread wakes up, takes the GIL and queues the next launches; the iteration queued behind a stop costs ~100 launches that return
+    at once.  ``final()`` after the loop answers for whatever has not been looked at.  Without it (a nested fit) ``check()`` is a stream synchronisation."""
     _tls = threading.local()
 
     def __init__(self, ctx, stop, lookahead):
@@ -209,6 +238,66 @@ class _StopWatch:
         return self._wait(k)
 
 
+class _Fit:
+    """Per-fit state: one object per call, never stored on the FitContext (one context serves several launching threads at once).  This base holds the
+    loop's device state -- stop flag, (prev_loss, loss) pair of the stop rule, step ticket of the fused tails, loss history --, the loss terms, the
+    current Adam groups and the fit's per-launch events (flushed to the caller's ``prof`` by FitContext._run_fit)."""
+
+    def __init__(self, dev, names, nsteps, prev_loss, prof):
+        self.terms = Terms(names, dev)
+        self.stop = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.loss_state = torch.full((2,), prev_loss, device=dev)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.hist = torch.full((nsteps,), float("nan"), device=dev)
+        self.lp = {"human": [], "object": []} if prof is not None else None
+        self.adam = None
+
+
+class _SmplFit(_Fit):
+    """Per-fit state of the SMPL-T pre-fit and the SMPL stage: pose / betas / trans (updated in place), pose_init and the SMPL-H forward / backward
+    buffers.  The fit adds its inputs: ``kpts``, ``temporal`` (SMPL-T); ``maps``, ``net_size``, ``crop_center``, ``body_center``, ``body_kpts``,
+    ``vert_order`` (SMPL stage)."""
+
+    def __init__(self, pose, betas, trans, names, nsteps, prev_loss, prof=None):
+        dev = pose.device; B = self.B = pose.shape[0]
+        super().__init__(dev, names, nsteps, prev_loss, prof)
+        self.pose, self.betas, self.trans = pose, betas, trans
+        self.verts = torch.empty(B, 6890, 3, device=dev); self.jtr = torch.empty(B, 52, 3, device=dev); self.vposed = torch.empty_like(self.verts)
+        self.ws = torch.empty(_lib().vt_smplh_workspace_floats(B), device=dev); self.scratch = torch.empty(_lib().vt_smplh_bwd_scratch_floats(B), device=dev)
+        self.dverts = torch.empty_like(self.verts); self.J = torch.empty(B, 25, 3, device=dev); self.dJ = torch.empty_like(self.J)
+        self.dpose = torch.empty(B, 156, device=dev); self.dbetas = torch.empty(B, 10, device=dev); self.dtrans = torch.empty(B, 3, device=dev)
+        self.vb = torch.empty(B, device=dev)
+        self.pose_init = pose.clone()
+
+    @property
+    def vert_order_ptr(self):
+        return self.vert_order.data_ptr() if self.vert_order is not None else None
+
+
+class _ObjectFit(_Fit):
+    """Per-fit state of the object stage: obj_R / obj_t (updated in place), the step buffers, the (B, 22) workspace in which the head of a fused step
+    leaves its SVD of M0 + noise for the tail of the same step, the silhouette buffers (with a SilSetup; ``img`` / ``per`` for the single-purpose step
+    only), the collision buffers (allocated by the first step that needs them) and the contact set (computed by the first 'joint' step).  The fit adds
+    its inputs: ``maps``, ``smpl_verts``, ``obj_s``, ``crop_center``, ``body_center``, ``occ``, ``noise``."""
+
+    def __init__(self, ctx, obj_R, obj_t, sil, nsteps, prof):
+        dev = obj_R.device; B = self.B = obj_R.shape[0]; N = self.N = ctx.obj_points.shape[0]; NV = self.NV = ctx.obj_verts.shape[0]
+        super().__init__(dev, ["object", "otemp", "ovtemp", "mask", "trans", "contact", "collide", "scale"], nsteps, 300.0, prof)   # prev_loss = 300
+        self.obj_R, self.obj_t, self.sil = obj_R, obj_t, sil
+        self.R = torch.empty(B, 3, 3, device=dev); self.X = torch.empty(B, N, 3, device=dev); self.dX = torch.empty_like(self.X)
+        self.svd_ws = torch.empty(B, 22, device=dev)
+        self.dR = torch.empty(B, 3, 3, device=dev); self.dM = torch.empty(B, 3, 3, device=dev); self.dt = torch.empty(B, 3, device=dev)
+        if sil is not None:
+            self.Vt = torch.empty(B, NV, 3, device=dev); self.dVt = torch.empty_like(self.Vt)
+            self.fidx = torch.empty(B, sil.size, sil.size, dtype=torch.int32, device=dev); self.dimg = torch.empty(B, sil.size, sil.size, device=dev)
+            self.sws = torch.empty(_lib().vt_sil_workspace_floats(B, NV, ctx.obj_faces.shape[0], sil.size), device=dev)
+            if not ctx.fused_steps:
+                self.img = torch.empty_like(self.dimg); self.per = torch.empty(B, device=dev)
+        self.trans_init = None          # phase 'sil'
+        self.Vc = self.cws = None       # collision term
+        self.contact = None             # 'Computing contacts once'
+
+
 class FitContext:
     """Device-resident constants shared by all batches of a sequence: SMPL-H model, body25 regressor, priors,
     SIF-Net decoders, part labels, object template / surface samples."""
@@ -223,27 +312,15 @@ class FitContext:
     # query per object-stage step instead of ~11, one tail instead of 8 in the SMPL stage); False = the single-purpose launches (same arithmetic in
     # the same order: the trajectories are bit-identical, tests/test_gpu_fit.py)
     fused_steps = os.environ.get("VT_FUSED_STEPS", "1") != "0"
-    # phase 'sil' of the fused step: the silhouette term as ONE call of 5 launches (vt_sil_step) instead of vt_sil_forward + vt_sil_mask_loss + vt_sil_backward
-    # (10 launches); bit-identical gradients (tests/test_gpu_parity.py::test_sil_step_equals_the_separate_launches)
-    fused_sil_step = os.environ.get("VT_FUSED_SIL_STEP", "1") != "0"
-    # phases 'object only' / 'sil': the temporal stencils inside the step's tail (vt_objstep_tail_temporal) instead of a launch of their own; bit-identical parameters
-    fused_tail_temporal = os.environ.get("VT_FUSED_TAIL_TEMPORAL", "1") != "0"
     # SMPL stage: keypoint chain as one launch + the query adding its gradient and the vertex acceleration stencil in its epilogue (vt_kpts_step /
     # vt_query_human_step: 8 launches per step instead of 11, bit-identical).  MEASURED SLOWER and therefore off: the twelve neighbour-frame loads per
     # point in the tail of the dominant kernel cost it 1 % (1.684 -> 1.700 ms), more than the three small launches it replaces were worth behind
     # the query (one stream 767.9 -> 777.8 ms per batch, two streams 690 -> 696; same box, two repetitions)
     fused_smpl_query = os.environ.get("VT_FUSED_SMPL_QUERY", "0") != "0"
-    # ... the keypoint chain alone as one launch BEHIND the query (vt_kpts_step, accumulate = 1) instead of vt_landmarks_forward + vt_kpts_loss + vt_landmarks_backward
-    fused_kpts_step = os.environ.get("VT_FUSED_KPTS_STEP", "1") != "0"
-    # object stage: the head of a fused step hands its SVD of M0 + noise to the step's tail (same numbers, one ~10 us decomposition less per step); 0: the tail decomposes again
-    share_step_svd = os.environ.get("VT_SHARE_STEP_SVD", "1") != "0"
-    # the query / SMPL-H launches queued behind the step that stopped a fit return at their first instruction (vt_stream_set_skip_flag)
+    # the query / SMPL-H launches queued behind the step that stopped a fit return at their first instruction (vt_stream_set_skip_flag); it also lets the
+    # host look at the stop flag one outer iteration late (_StopWatch) -- the bubble a slow or contended host (8 ranks x 2 launching threads on one node)
+    # would otherwise pay once per outer iteration
     device_skip = os.environ.get("VT_DEVICE_SKIP", "1") != "0"
-    # the host looks at the stop flag of outer iteration k only after it has queued iteration k + 1 (asynchronous copy of the flag to pinned memory + an
-    # event per iteration): the stream never runs dry while the launching thread wakes up, takes the GIL and queues the next launches -- the bubble a
-    # slow or contended host (8 ranks x 2 launching threads on one node) pays once per outer iteration.  Needs the device-side skip: the iteration
-    # queued behind a stop then costs ~100 launches that return at once instead of ten Adam steps; results are unchanged either way.
-    stop_lookahead = os.environ.get("VT_STOP_LOOKAHEAD", "1") != "0"
 
     def __init__(self, smpl_model, regressors, priors, decoders=None, part_labels=None, obj_verts=None, obj_faces=None, obj_points=None,
                  cam=ops.DEFAULT_CAM, device="cuda:0"):
@@ -328,6 +405,33 @@ class FitContext:
                                    scratch_b.data_ptr(), dpose.data_ptr(), w / B, L.stream_ptr()))
         _chk(_lib().vt_sum_to_term(scratch_b.data_ptr(), B, 1.0 / B, terms.ptr(name), L.stream_ptr()))
 
+    # ---- the fit loop shared by the three fits ------------------------------------------------------------
+    def _run_fit(self, f, start, end, check_every, outer, prof=None):
+        """Outer iterations ``start`` .. ``end`` of 10 Adam steps each: ``outer(it)`` sets up iteration ``it`` (phase, Adam groups, decayed weights) and
+        returns (step, phase, w, armed); ``step(f, phase, k, w, armed)`` queues the launches of step k of the fit (its slot in the loss history; also
+        the step index of its per-launch events).  The host looks at the device-side stop flag every ``check_every`` outer iterations; after an early
+        stop the steps are recounted from the loss history (the steps queued behind the stop step wrote nothing)."""
+        res = FitResult()
+        with self._skip_after_stop(f.stop) as skipping:
+            watch = _StopWatch(self, f.stop, skipping)
+            for it in range(start, end):
+                step, phase, w, armed = outer(it)
+                for i in range(10):
+                    step(f, phase, (it - start) * 10 + i, w, armed)
+                res.steps += 10
+                res.outer_iters += 1
+                if (it - start) % check_every == check_every - 1 and watch.check():
+                    res.stopped_early = True
+                    break
+            res.stopped_early = res.stopped_early or watch.final()
+        res.losses = f.hist.cpu().numpy()
+        if res.stopped_early:
+            res.steps = int(np.isfinite(res.losses).sum())
+            res.outer_iters = -(-res.steps // 10)          # (with the look-ahead one more iteration was queued; its launches returned at once)
+        _flush_events(prof, f.lp, res.steps if (res.stopped_early and self.device_skip) else None)
+        _check_finite(res, "fit")
+        return res
+
     # ---- SMPL-T pre-fit (fit_SMPLH_kpts.py:114-180) ------------------------------------------------------
     def fit_smplt(self, pose, betas, trans, kpts, max_iter=100, iter_for_global=8, temporal=True, pinit_w=900.0,
                   lr_global=0.01, lr_all=0.001, it_range=None, check_every=1, weights=None, early_stop=True):
@@ -339,66 +443,24 @@ class FitContext:
             return self._fit_smplt(pose, betas, trans, kpts, max_iter, iter_for_global, temporal, pinit_w, lr_global, lr_all, it_range, check_every, weights, early_stop)
 
     def _fit_smplt(self, pose, betas, trans, kpts, max_iter, iter_for_global, temporal, pinit_w, lr_global, lr_all, it_range, check_every, weights, early_stop=True):
-        dev = pose.device; B = pose.shape[0]
         _require_params(pose, betas, trans)
-        kpts = _as_input(kpts, dev)
-        names = ["kpts", "temp", "ptemp", "pose", "pinit", "hand"]
-        terms = Terms(names, dev)
         table = dict(SMPLT_WEIGHTS); table["pinit"] = pinit_w
         if weights is not None:
             table.update({k: float(v) for k, v in weights.items() if k in table})
-        verts = torch.empty(B, 6890, 3, device=dev); jtr = torch.empty(B, 52, 3, device=dev); vposed = torch.empty_like(verts)
-        ws = torch.empty(_lib().vt_smplh_workspace_floats(B), device=dev); scratch = torch.empty(_lib().vt_smplh_bwd_scratch_floats(B), device=dev)
-        dverts = torch.empty_like(verts); J = torch.empty(B, 25, 3, device=dev); dJ = torch.empty_like(J)
-        dpose = torch.empty(B, 156, device=dev); dbetas = torch.empty(B, 10, device=dev); dtrans = torch.empty(B, 3, device=dev)
-        vb = torch.empty(B, device=dev)
-        pose_init = pose.clone()
-        stop = torch.zeros(1, dtype=torch.int32, device=dev); state = torch.zeros(2, device=dev)   # prev_loss = 0 (fit_SMPLH_kpts.py:136)
-        self.hand_prior_value(pose, terms, "hand", vb)
         start, end = it_range if it_range is not None else (0, max_iter)
-        hist = torch.full(((end - start) * 10,), float("nan"), device=dev)
-        temporal = temporal and B >= 3
-        adam = None
-        res = FitResult()
-        with self._skip_after_stop(stop) as skipping:
-            watch = self._stop_watch(stop, skipping)
-            for it in range(start, end):
-                if adam is None or it == iter_for_global:
-                    if it < iter_for_global:      # init_globalpose_optimizer: trans, global_pose, top_betas
-                        adam = AdamState([(trans, 3, dtrans, lr_global), (pose, 3, dpose, lr_global), (betas, 2, dbetas, lr_global)], stop)
-                    else:                         # init_allpose_optimizer: trans, global, body, top_betas, other_betas
-                        adam = AdamState([(trans, 3, dtrans, lr_all), (pose, 66, dpose, lr_all), (betas, 10, dbetas, lr_all)], stop)
-                decay = it // 3
-                w = terms.weights(table, decay)
-                for i in range(10):
-                    terms.zero(0, 5)
-                    self.smpl_forward(pose, betas, trans, verts, jtr, vposed, ws)
-                    _chk(_lib().vt_landmarks_forward(self.b25.h, verts.data_ptr(), B, J.data_ptr(), L.stream_ptr()))
-                    _chk(_lib().vt_kpts_loss(J.data_ptr(), kpts.data_ptr(), None, B, 25, 0, self.cam.ctypes.data, 0.0, float(w[0]), terms.ptr("kpts"), dJ.data_ptr(), L.stream_ptr()))
-                    _chk(_lib().vt_landmarks_backward(self.b25.h, dJ.data_ptr(), B, dverts.data_ptr(), 0, L.stream_ptr()))
-                    if temporal:
-                        _chk(_lib().vt_accel_loss(verts.data_ptr(), B, 6890 * 3, None, float(w[1]), terms.ptr("temp"), dverts.data_ptr(), L.stream_ptr()))
-                    self.smpl_backward(pose, betas, dverts, vposed, ws, scratch, dpose, dbetas, dtrans)
-                    if temporal:
-                        _chk(_lib().vt_accel_loss_strided(pose.data_ptr(), B, 66, 156, self.jw66.data_ptr(), float(w[2]), terms.ptr("ptemp"), dpose.data_ptr(), L.stream_ptr()))
-                    self.body_prior(pose, dpose, float(w[3]), terms, "pose", vb)
-                    _chk(_lib().vt_sqdiff_loss(pose.data_ptr() + 12, 156, pose_init.data_ptr() + 12, 156, B, 63, float(B * 63), float(w[4]),
-                                               terms.ptr("pinit"), dpose.data_ptr() + 12, L.stream_ptr()))
-                    adam.step()
-                    _chk(_lib().vt_loss_reduce_and_stop(terms.buf.data_ptr(), w.ctypes.data, len(names), 1e-3, int(early_stop and it > 0.3 * max_iter), state.data_ptr(),
-                                                        stop.data_ptr(), hist.data_ptr(), (it - start) * 10 + i, L.stream_ptr()))
-                    res.steps += 1
-                res.outer_iters += 1
-                if (it - start) % check_every == check_every - 1 and watch.check():
-                    res.stopped_early = True
-                    break
-            res.stopped_early = res.stopped_early or watch.final()
-        res.losses = hist.cpu().numpy()
-        if res.stopped_early:
-            res.steps = int(np.isfinite(res.losses).sum())
-            res.outer_iters = -(-res.steps // 10)          # (with the look-ahead one more iteration was queued; its launches returned at once)
-        _check_finite(res, "fit")
-        return res
+        f = _SmplFit(pose, betas, trans, ["kpts", "temp", "ptemp", "pose", "pinit", "hand"], (end - start) * 10, 0.0)   # prev_loss = 0 (fit_SMPLH_kpts.py:136)
+        f.kpts = _as_input(kpts, pose.device)
+        f.temporal = temporal and f.B >= 3
+        self.hand_prior_value(pose, f.terms, "hand", f.vb)
+
+        def outer(it):
+            if f.adam is None or it == iter_for_global:
+                if it < iter_for_global:      # init_globalpose_optimizer: trans, global_pose, top_betas
+                    f.adam = AdamState([(trans, 3, f.dtrans, lr_global), (pose, 3, f.dpose, lr_global), (betas, 2, f.dbetas, lr_global)], f.stop)
+                else:                         # init_allpose_optimizer: trans, global, body, top_betas, other_betas
+                    f.adam = AdamState([(trans, 3, f.dtrans, lr_all), (pose, 66, f.dpose, lr_all), (betas, 10, f.dbetas, lr_all)], f.stop)
+            return self._smplt_step, None, f.terms.weights(table, it // 3), int(early_stop and it > 0.3 * max_iter)
+        return self._run_fit(f, start, end, check_every, outer)
 
     # ---- fit, SMPL stage (recon_fit_behave.py:393-513) ----------------------------------------------------
     def optimize_smpl(self, maps, pose, betas, trans, crop_center, body_center, body_kpts, max_iter=100, iter_for_betas=1,
@@ -413,112 +475,45 @@ class FitContext:
 
     def _optimize_smpl(self, maps, pose, betas, trans, crop_center, body_center, body_kpts, max_iter, iter_for_betas, iter_for_pose, iter_for_kpts,
                        it_range, net_size, check_every, prof, early_stop=True):
-        dev = pose.device; B = pose.shape[0]; V = 6890
+        dev = pose.device
         _require_params(pose, betas, trans)
-        crop_center, body_center, body_kpts = _as_input(crop_center, dev), _as_input(body_center, dev), _as_input(body_kpts, dev)
-        if self.use_projection and self.net.precision != "fp32" and not maps.force_fp32:
-            maps.build_projection(self.net)     # rebuilt at every call: 2.5 ms per 96-frame batch, never stale (and at the maps' range level)
-        names = ["df_h", "part", "pose", "pinit", "j2d", "stemp", "hand"]
-        vert_order = self.vert_order
-        terms = Terms(names, dev)
-        verts = torch.empty(B, V, 3, device=dev); jtr = torch.empty(B, 52, 3, device=dev); vposed = torch.empty_like(verts)
-        ws = torch.empty(_lib().vt_smplh_workspace_floats(B), device=dev); scratch = torch.empty(_lib().vt_smplh_bwd_scratch_floats(B), device=dev)
-        dverts = torch.empty_like(verts); J = torch.empty(B, 25, 3, device=dev); dJ = torch.empty_like(J)
-        dpose = torch.empty(B, 156, device=dev); dbetas = torch.empty(B, 10, device=dev); dtrans = torch.empty(B, 3, device=dev)
-        vb = torch.empty(B, device=dev)
-        pose_init = pose.clone()
-        stop = torch.zeros(1, dtype=torch.int32, device=dev)
-        lp = {"human": [], "object": []} if prof is not None else None      # this fit's per-launch events (flushed to ``prof`` below)
-        state = torch.tensor([300.0, 300.0], device=dev)          # prev_loss = 300 (recon_fit_behave.py:408)
-        fused = bool(self.fused_steps); ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         split_route = self.net.precision != "fp32" and not maps.force_fp32          # the step forms of the query exist on the split-f16 route only
+        if self.use_projection and split_route:
+            maps.build_projection(self.net)     # rebuilt at every call: 2.5 ms per 96-frame batch, never stale (and at the maps' range level)
+        total = iter_for_betas + iter_for_kpts + iter_for_pose + max_iter
+        start, end = it_range if it_range is not None else (0, total)
+        f = _SmplFit(pose, betas, trans, ["df_h", "part", "pose", "pinit", "j2d", "stemp", "hand"], (end - start) * 10, 300.0, prof)  # prev_loss = 300 (recon_fit_behave.py:408)
+        f.maps, f.net_size = maps, net_size
+        f.crop_center, f.body_center, f.body_kpts = _as_input(crop_center, dev), _as_input(body_center, dev), _as_input(body_kpts, dev)
+        f.vert_order = self.vert_order
         if self.sort_query_points:
             # processing order for this batch: Morton order of the IMAGE positions of the initial vertices of the middle frame (the body moves
             # little inside a batch and during the fit); a little better than the template's 3-D order because the perspective maps -- the
             # projection rows and tmpx, two thirds of the gathered bytes -- see exactly this neighbourhood structure.  Results do not depend on it.
             # Computed on the device (bit interleave + one argsort of 6890 keys): no host round trip inside the batch.
-            self.smpl_forward(pose, betas, trans, verts, jtr, vposed, ws)
-            v0 = verts[B // 2]
-            vert_order = morton_order_device(torch.stack([v0[:, 0] / v0[:, 2], v0[:, 1] / v0[:, 2]], 1))
-        self.hand_prior_value(pose, terms, "hand", vb)
-        total = iter_for_betas + iter_for_kpts + iter_for_pose + max_iter
-        start, end = it_range if it_range is not None else (0, total)
-        hist = torch.full(((end - start) * 10,), float("nan"), device=dev)
+            self.smpl_forward(pose, betas, trans, f.verts, f.jtr, f.vposed, f.ws)
+            v0 = f.verts[f.B // 2]
+            f.vert_order = morton_order_device(torch.stack([v0[:, 0] / v0[:, 2], v0[:, 1] / v0[:, 2]], 1))
+        self.hand_prior_value(pose, f.terms, "hand", f.vb)
+        if not self.fused_steps:
+            step = self._smpl_step
+        elif split_route and self.fused_smpl_query:
+            step = self._smpl_step_fused_query
+        else:
+            step = self._smpl_step_fused
         arm_after = 0.25 * max_iter + iter_for_betas + iter_for_pose
-        adam = None; res = FitResult()
-        with self._skip_after_stop(stop) as skipping:
-            watch = self._stop_watch(stop, skipping)
-            for it in range(start, end):
-                if it < iter_for_betas:
-                    phase = "global"
-                    if adam is None:
-                        adam = AdamState([(betas, 2, dbetas, 0.02), (trans, 3, dtrans, 0.02)], stop)
-                else:
-                    phase = "kpts" if it >= iter_for_betas + iter_for_pose else "smpl all pose"
-                    if adam is None or it == iter_for_betas:
-                        adam = AdamState([(trans, 3, dtrans, 0.006), (pose, 66, dpose, 0.006), (betas, 10, dbetas, 0.006)], stop)
-                decay = 1 if phase != "kpts" else it / 3
-                w = terms.weights(FIT_WEIGHTS, decay)
-                for i in range(10):
-                    if not fused:
-                        terms.zero(0, 6)        # (fused: the tail of the previous step left them zeroed)
-                    self.smpl_forward(pose, betas, trans, verts, jtr, vposed, ws)
-                    if fused and split_route and self.fused_smpl_query:
-                        # keypoint chain (joints, 2-D term, its gradient written to dverts) in one launch, then the query adds its gradient and the vertex
-                        # acceleration stencil in its own epilogue: 8 launches per step with the two forward and three backward SMPL-H kernels and the tail
-                        if phase == "kpts":
-                            _chk(_lib().vt_kpts_step(self.b25.h, verts.data_ptr(), body_kpts.data_ptr(), crop_center.data_ptr(), B, 1, self.cam.ctypes.data, net_size,
-                                                     float(w[4]), terms.ptr("j2d"), J.data_ptr(), dverts.data_ptr(), 0, L.stream_ptr()))
-                        ev = _ev_begin(lp)
-                        _chk(_lib().vt_query_human_step(self.net.h, C.byref(maps.c), verts.data_ptr(), crop_center.data_ptr(), body_center.data_ptr(), B, V,
-                                                        self.labels.data_ptr(), vert_order.data_ptr() if vert_order is not None else None, float(w[0]), float(w[1]),
-                                                        int(phase == "kpts"), float(w[5]), terms.ptr("stemp") if B >= 4 else None, dverts.data_ptr(), terms.ptr("df_h"),
-                                                        L.stream_ptr()))
-                        _ev_end(lp, "human", ev, B, res.steps)
-                        self.smpl_backward(pose, betas, dverts, vposed, ws, scratch, dpose, dbetas, dtrans)
-                        self._smpl_tail(pose, pose_init, dpose, B, w, terms, names, adam, state, stop, hist, (it - start) * 10 + i, ticket, int(early_stop and it > arm_after))
-                        res.steps += 1
-                        continue
-                    ev = _ev_begin(lp)
-                    _chk(_lib().vt_query_human_loss(self.net.h, C.byref(maps.c), verts.data_ptr(), crop_center.data_ptr(), body_center.data_ptr(), B, V,
-                                                    self.labels.data_ptr(), vert_order.data_ptr() if vert_order is not None else None, float(w[0]), float(w[1]),
-                                                    dverts.data_ptr(), terms.ptr("df_h"), L.stream_ptr()))
-                    _ev_end(lp, "human", ev, B, res.steps)
-                    if phase == "kpts" and fused and self.fused_kpts_step:
-                        # joints, 2-D keypoint term and its gradient ADDED to the query's (accumulate = 1: the float addition of vt_landmarks_backward) in one launch
-                        _chk(_lib().vt_kpts_step(self.b25.h, verts.data_ptr(), body_kpts.data_ptr(), crop_center.data_ptr(), B, 1, self.cam.ctypes.data, net_size,
-                                                 float(w[4]), terms.ptr("j2d"), J.data_ptr(), dverts.data_ptr(), 1, L.stream_ptr()))
-                    elif phase == "kpts":
-                        _chk(_lib().vt_landmarks_forward(self.b25.h, verts.data_ptr(), B, J.data_ptr(), L.stream_ptr()))
-                        _chk(_lib().vt_kpts_loss(J.data_ptr(), body_kpts.data_ptr(), crop_center.data_ptr(), B, 25, 1, self.cam.ctypes.data, net_size,
-                                                 float(w[4]), terms.ptr("j2d"), dJ.data_ptr(), L.stream_ptr()))
-                        _chk(_lib().vt_landmarks_backward(self.b25.h, dJ.data_ptr(), B, dverts.data_ptr(), 1, L.stream_ptr()))
-                    if B >= 4:
-                        _chk(_lib().vt_accel_loss(verts.data_ptr(), B, V * 3, None, float(w[5]), terms.ptr("stemp"), dverts.data_ptr(), L.stream_ptr()))
-                    self.smpl_backward(pose, betas, dverts, vposed, ws, scratch, dpose, dbetas, dtrans)
-                    if fused:
-                        self._smpl_tail(pose, pose_init, dpose, B, w, terms, names, adam, state, stop, hist, (it - start) * 10 + i, ticket, int(early_stop and it > arm_after))
-                    else:
-                        self.body_prior(pose, dpose, float(w[2]), terms, "pose", vb)
-                        # pinit = mean_B sum (pose[:, 3:72] - pose_init)^2
-                        _chk(_lib().vt_sqdiff_loss(pose.data_ptr() + 12, 156, pose_init.data_ptr() + 12, 156, B, 69, float(B), float(w[3]),
-                                                   terms.ptr("pinit"), dpose.data_ptr() + 12, L.stream_ptr()))
-                        adam.step()
-                        _chk(_lib().vt_loss_reduce_and_stop(terms.buf.data_ptr(), w.ctypes.data, len(names), 1e-3, int(early_stop and it > arm_after), state.data_ptr(),
-                                                            stop.data_ptr(), hist.data_ptr(), (it - start) * 10 + i, L.stream_ptr()))
-                    res.steps += 1
-                res.outer_iters += 1
-                if (it - start) % check_every == check_every - 1 and watch.check():
-                    res.stopped_early = True
-                    break
-            res.stopped_early = res.stopped_early or watch.final()
-        res.losses = hist.cpu().numpy()
-        if res.stopped_early:
-            res.steps = int(np.isfinite(res.losses).sum())
-            res.outer_iters = -(-res.steps // 10)          # (with the look-ahead one more iteration was queued; its launches returned at once)
-        _flush_events(prof, lp, res.steps if (res.stopped_early and self.device_skip) else None)
-        _check_finite(res, "fit")
-        return res
+
+        def outer(it):
+            if it < iter_for_betas:
+                phase = "global"
+                if f.adam is None:
+                    f.adam = AdamState([(betas, 2, f.dbetas, 0.02), (trans, 3, f.dtrans, 0.02)], f.stop)
+            else:
+                phase = "kpts" if it >= iter_for_betas + iter_for_pose else "smpl all pose"
+                if f.adam is None or it == iter_for_betas:
+                    f.adam = AdamState([(trans, 3, f.dtrans, 0.006), (pose, 66, f.dpose, 0.006), (betas, 10, f.dbetas, 0.006)], f.stop)
+            return step, phase, f.terms.weights(FIT_WEIGHTS, 1 if phase != "kpts" else it / 3), int(early_stop and it > arm_after)
+        return self._run_fit(f, start, end, check_every, outer, prof)
 
     # ---- fit, object stage (recon_fit_trivis_full.py:283-377) ----------------------------------------------
     def optimize_smpl_object(self, maps, smpl_verts, obj_R, obj_t, obj_s, crop_center, body_center, occ, sil=None, noise=None,
@@ -533,136 +528,50 @@ class FitContext:
 
     def _optimize_smpl_object(self, maps, smpl_verts, obj_R, obj_t, obj_s, crop_center, body_center, occ, sil, noise, iter_for_obj, iter_for_sil,
                               joint_iter, max_iter, it_range, seed, check_every, prof, early_stop=True):
-        dev = obj_R.device; B = obj_R.shape[0]; N = self.obj_points.shape[0]; NV = self.obj_verts.shape[0]
+        dev = obj_R.device; B = obj_R.shape[0]
         _require_params(obj_R, obj_t)
-        smpl_verts, obj_s, crop_center, body_center, occ = (_as_input(x, dev) for x in (smpl_verts, obj_s, crop_center, body_center, occ))
-        obj_s = obj_s.reshape(-1)
-        if noise is not None:
-            noise = _as_input(noise, dev)
         if self.use_projection and self.net.precision != "fp32" and not maps.force_fp32:
             maps.build_projection(self.net)
-        names = ["object", "otemp", "ovtemp", "mask", "trans", "contact", "collide", "scale"]
-        terms = Terms(names, dev)
         total = joint_iter + iter_for_obj + max_iter + iter_for_sil
         start, end = it_range if it_range is not None else (0, total)
-        nsteps = (end - start) * 10
-        if noise is None:
+        f = _ObjectFit(self, obj_R, obj_t, sil, (end - start) * 10, prof)
+        f.maps = maps
+        f.smpl_verts, f.obj_s, f.crop_center, f.body_center, f.occ = (_as_input(x, dev) for x in (smpl_verts, obj_s, crop_center, body_center, occ))
+        f.obj_s = f.obj_s.reshape(-1)
+        if noise is not None:
+            f.noise = _as_input(noise, dev)
+        else:
             gen = torch.Generator(device=dev); gen.manual_seed(seed)
-            noise = torch.rand(nsteps, B, 3, 3, device=dev, generator=gen)
-        R = torch.empty(B, 3, 3, device=dev); X = torch.empty(B, N, 3, device=dev); dX = torch.empty_like(X)
-        # head -> tail hand-over of a fused step's SVD (vt_objstep_head decomposes M0 + noise, the tail's SO(3) VJP needs the same decomposition)
-        R._vt_svd_ws = torch.empty(B, 22, device=dev) if self.share_step_svd else None
-        dR = torch.empty(B, 3, 3, device=dev); dM = torch.empty(B, 3, 3, device=dev); dt = torch.empty(B, 3, device=dev)
-        stop = torch.zeros(1, dtype=torch.int32, device=dev); state = torch.tensor([300.0, 300.0], device=dev)
-        lp = {"human": [], "object": []} if prof is not None else None
-        ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        hist = torch.full((nsteps,), float("nan"), device=dev)
-        Rv, tv = obj_R.view(B, 9), obj_t
-        if sil is not None:
-            Vt = torch.empty(B, NV, 3, device=dev); dVt = torch.empty_like(Vt); img = torch.empty(B, sil.size, sil.size, device=dev)
-            fidx = torch.empty(B, sil.size, sil.size, dtype=torch.int32, device=dev)
-            sws = torch.empty(_lib().vt_sil_workspace_floats(B, NV, self.obj_faces.shape[0], sil.size), device=dev)
-            dimg = torch.empty_like(img); per = torch.empty(B, device=dev)
-        adam = None; res = FitResult(); contact = None; trans_init = None; cws = None; Vc = None
-        contact_box = [None]        # 'Computing contacts once': filled by the first step of phase 'joint', whichever step form runs it
+            f.noise = torch.rand((end - start) * 10, B, 3, 3, device=dev, generator=gen)
         # 'scale' = mean((obj_s - 1)^2) (recon_fit_trivis_full.py:161,227): obj_s is never optimised, so the term is a constant of the call
         # -- zero for the obj_s == 1 that fit_recon passes -- but it is part of the summed loss the stop rule looks at
-        ones = torch.ones_like(obj_s)
-        _chk(_lib().vt_sqdiff_loss(obj_s.data_ptr(), 1, ones.data_ptr(), 1, B, 1, float(B), 0.0, terms.ptr("scale"), None, L.stream_ptr()))
-        with self._skip_after_stop(stop) as skipping:
-            watch = self._stop_watch(stop, skipping)
-            for it in range(start, end):
-                if it < iter_for_obj:
-                    phase = "object only"
-                    if adam is None:
-                        adam = AdamState([(Rv, 9, dM.view(B, 9), 0.002), (tv, 3, dt, 0.006)], stop)
-                elif it < iter_for_obj + iter_for_sil:
-                    phase = "sil"
-                    if adam is None or it == iter_for_obj:
-                        adam = AdamState([(Rv, 9, dM.view(B, 9), 0.006), (tv, 3, dt, 0.006)], stop)
-                        trans_init = obj_t.clone()
-                else:
-                    phase = "joint"
-                    if adam is None or it == iter_for_obj + iter_for_sil:
-                        adam = AdamState([(tv, 3, dt, 0.002)], stop)
-                decay = 1 if phase == "object only" else (it - iter_for_obj + 1 if phase == "sil" else (it - iter_for_obj + 1) / 3)
-                tw = 10.0 if phase == "joint" else 1.0
-                w = terms.weights(FIT_WEIGHTS, decay, {"otemp": tw, "ovtemp": tw})
-                # the fused step launches cover everything but the interpenetration term (it adds to dt between the rigid VJP and the SO(3) VJP)
-                fused = bool(self.fused_steps) and not (phase == "joint" and self.collision_loss)
-                for i in range(10):
-                    k = (it - start) * 10 + i
-                    nz = noise[k]
-                    if fused:
-                        if phase == "sil" and sil is None:
-                            raise L.VtError("phase 'sil' needs a SilSetup")
-                        self._object_step_fused(phase, maps, nz, obj_R, obj_t, obj_s, crop_center, body_center, occ, sil, w, terms, names, adam, B, N, NV, R, X, dX, dR, dM, dt,
-                                                Vt if sil is not None else None, dVt if sil is not None else None, img if sil is not None else None,
-                                                fidx if sil is not None else None, sws if sil is not None else None, dimg if sil is not None else None,
-                                                per if sil is not None else None, trans_init, smpl_verts, lp, state, stop, hist, k, ticket,
-                                                int(early_stop and phase == "joint" and it > 0.25 * max_iter), contact_box)
-                        res.steps += 1
-                        continue
-                    terms.zero(0, 7)
-                    _chk(_lib().vt_so3_project_forward(obj_R.data_ptr(), nz.data_ptr(), B, R.data_ptr(), L.stream_ptr()))
-                    _chk(_lib().vt_rigid_forward(self.obj_points.data_ptr(), 1, R.data_ptr(), obj_t.data_ptr(), obj_s.data_ptr(), B, N, X.data_ptr(), L.stream_ptr()))
-                    acc = 0
-                    if phase == "sil":
-                        if sil is None:
-                            raise L.VtError("phase 'sil' needs a SilSetup")
-                        _chk(_lib().vt_fill(dX.data_ptr(), dX.numel(), 0.0, L.stream_ptr()))
-                    else:
-                        ev = _ev_begin(lp)
-                        _chk(_lib().vt_query_object_loss(self.net.h, C.byref(maps.c), X.data_ptr(), crop_center.data_ptr(), body_center.data_ptr(), B, N,
-                                                         occ.data_ptr(), float(w[0]), dX.data_ptr(), terms.ptr("object"), L.stream_ptr()))
-                        _ev_end(lp, "object", ev, B, res.steps)
-                    if B >= 4:
-                        _chk(_lib().vt_accel_loss(X.data_ptr(), B, N * 3, None, float(w[1]), terms.ptr("otemp"), dX.data_ptr(), L.stream_ptr()))
-                        _chk(_lib().vt_velocity_loss(X.data_ptr(), B, N * 3, float(w[2]), terms.ptr("ovtemp"), dX.data_ptr(), L.stream_ptr()))
-                    if phase == "sil":
-                        _chk(_lib().vt_rigid_forward(self.obj_verts.data_ptr(), 1, R.data_ptr(), obj_t.data_ptr(), obj_s.data_ptr(), B, NV, Vt.data_ptr(), L.stream_ptr()))
-                        _chk(_lib().vt_sil_forward(Vt.data_ptr(), B, NV, self.obj_faces.data_ptr(), self.obj_faces.shape[0], sil.K.data_ptr(), sil.size,
-                                                   img.data_ptr(), fidx.data_ptr(), sws.data_ptr(), L.stream_ptr()))
-                        _chk(_lib().vt_sil_mask_loss(img.data_ptr(), sil.keep.data_ptr(), sil.ref.data_ptr(), occ.data_ptr(), B, sil.size, float(w[3]),
-                                                     terms.ptr("mask"), per.data_ptr(), dimg.data_ptr(), L.stream_ptr()))
-                        _chk(_lib().vt_sil_backward(Vt.data_ptr(), B, NV, self.obj_faces.data_ptr(), self.obj_faces.shape[0], sil.K.data_ptr(), sil.size,
-                                                    fidx.data_ptr(), dimg.data_ptr(), 1e-4, sws.data_ptr(), dVt.data_ptr(), L.stream_ptr()))
-                        _chk(_lib().vt_rigid_backward(self.obj_verts.data_ptr(), 1, obj_s.data_ptr(), B, NV, dVt.data_ptr(), dR.data_ptr(), dt.data_ptr(), 0, L.stream_ptr()))
-                        _chk(_lib().vt_sqdiff_loss(obj_t.data_ptr(), 3, trans_init.data_ptr(), 3, B, 3, float(B * 3), float(w[4]), terms.ptr("trans"), dt.data_ptr(), L.stream_ptr()))
-                        acc = 1
-                    if phase == "joint":
-                        if contact_box[0] is None:
-                            contact_box[0] = self._contacts_once(maps, smpl_verts, X, crop_center, body_center)
-                        contact = contact_box[0]
-                        if contact["P"] > 0:
-                            self._contact_term(contact, X, dX, float(w[5]), terms)
-                    _chk(_lib().vt_rigid_backward(self.obj_points.data_ptr(), 1, obj_s.data_ptr(), B, N, dX.data_ptr(), dR.data_ptr(), dt.data_ptr(), acc, L.stream_ptr()))
-                    if phase == "joint" and self.collision_loss:
-                        # prevent interpenetration (recon_fit_trivis_full.py:260-264): SMPL mesh vs the transformed object template
-                        if cws is None:
-                            Vc = torch.empty(B, NV, 3, device=dev)
-                            cws = torch.empty((_lib().vt_collision_workspace_bytes(B, self.smpl_faces.shape[0]) + 7) // 8, dtype=torch.int64, device=dev)
-                        _chk(_lib().vt_rigid_forward(self.obj_verts.data_ptr(), 1, R.data_ptr(), obj_t.data_ptr(), obj_s.data_ptr(), B, NV, Vc.data_ptr(), L.stream_ptr()))
-                        _chk(_lib().vt_collision_loss(smpl_verts.data_ptr(), smpl_verts.shape[1], self.smpl_faces.data_ptr(), self.smpl_faces.shape[0], Vc.data_ptr(), NV,
-                                                      self.obj_faces.data_ptr(), self.obj_faces.shape[0], B, 0.5, 8, float(w[6]), terms.ptr("collide"), dt.data_ptr(), None,
-                                                      cws.data_ptr(), L.stream_ptr()))
-                    _chk(_lib().vt_so3_project_backward(obj_R.data_ptr(), nz.data_ptr(), B, dR.data_ptr(), dM.data_ptr(), L.stream_ptr()))
-                    adam.step()
-                    _chk(_lib().vt_loss_reduce_and_stop(terms.buf.data_ptr(), w.ctypes.data, len(names), 1e-4, int(early_stop and phase == "joint" and it > 0.25 * max_iter),
-                                                        state.data_ptr(), stop.data_ptr(), hist.data_ptr(), k, L.stream_ptr()))
-                    res.steps += 1
-                res.outer_iters += 1
-                if (it - start) % check_every == check_every - 1 and watch.check():
-                    res.stopped_early = True
-                    break
-            res.stopped_early = res.stopped_early or watch.final()
-        res.losses = hist.cpu().numpy()
-        if res.stopped_early:
-            res.steps = int(np.isfinite(res.losses).sum())
-            res.outer_iters = -(-res.steps // 10)          # (with the look-ahead one more iteration was queued; its launches returned at once)
-        _flush_events(prof, lp, res.steps if (res.stopped_early and self.device_skip) else None)
-        _check_finite(res, "fit")
-        return res
+        ones = torch.ones_like(f.obj_s)
+        _chk(_lib().vt_sqdiff_loss(f.obj_s.data_ptr(), 1, ones.data_ptr(), 1, B, 1, float(B), 0.0, f.terms.ptr("scale"), None, L.stream_ptr()))
+        Rv, dMv = obj_R.view(B, 9), f.dM.view(B, 9)
+
+        def outer(it):
+            if it < iter_for_obj:
+                phase = "object only"
+                if f.adam is None:
+                    f.adam = AdamState([(Rv, 9, dMv, 0.002), (obj_t, 3, f.dt, 0.006)], f.stop)
+            elif it < iter_for_obj + iter_for_sil:
+                phase = "sil"
+                if sil is None:
+                    raise L.VtError("phase 'sil' needs a SilSetup")
+                if f.adam is None or it == iter_for_obj:
+                    f.adam = AdamState([(Rv, 9, dMv, 0.006), (obj_t, 3, f.dt, 0.006)], f.stop)
+                    f.trans_init = obj_t.clone()
+            else:
+                phase = "joint"
+                if f.adam is None or it == iter_for_obj + iter_for_sil:
+                    f.adam = AdamState([(obj_t, 3, f.dt, 0.002)], f.stop)
+            decay = 1 if phase == "object only" else (it - iter_for_obj + 1 if phase == "sil" else (it - iter_for_obj + 1) / 3)
+            tw = 10.0 if phase == "joint" else 1.0
+            w = f.terms.weights(FIT_WEIGHTS, decay, {"otemp": tw, "ovtemp": tw})
+            # the fused step launches cover everything but the interpenetration term (it adds to dt between the rigid VJP and the SO(3) VJP)
+            fused = self.fused_steps and not (phase == "joint" and self.collision_loss)
+            return (self._object_step_fused if fused else self._object_step), phase, w, int(early_stop and phase == "joint" and it > 0.25 * max_iter)
+        return self._run_fit(f, start, end, check_every, outer, prof)
 
     def _read_stop(self, stop):
         """the host's look at the device-side stop flag, once per outer iteration: a stream synchronisation.  ``host_wait_s`` accumulates the time the host
@@ -695,81 +604,187 @@ class FitContext:
         finally:
             _lib().vt_stream_set_skip_flag(sp, None)
 
-    def _stop_watch(self, stop, skipping):
-        """the host's view of the stop flag for one fit: with the look-ahead (needs ``skipping``, the device-side skip) ``check()`` after queuing outer
-        iteration k answers for iteration k - 1; ``final()`` after the loop answers for whatever has not been looked at"""
-        return _StopWatch(self, stop, bool(skipping and self.stop_lookahead))
+    # ---- Adam steps: step(f, phase, k, w, armed) queues step k of fit ``f`` (see _run_fit) -------------------
+    def _smplt_step(self, f, phase, k, w, armed):
+        """one Adam step of the SMPL-T pre-fit (SMPLHFitter30fps.compute_loss, fit_SMPLH_30fps.py:153-200)"""
+        lib = _lib(); st = L.stream_ptr(); B = f.B; pose = f.pose
+        f.terms.zero(0, 5)
+        self.smpl_forward(pose, f.betas, f.trans, f.verts, f.jtr, f.vposed, f.ws)
+        _chk(lib.vt_landmarks_forward(self.b25.h, f.verts.data_ptr(), B, f.J.data_ptr(), st))
+        _chk(lib.vt_kpts_loss(f.J.data_ptr(), f.kpts.data_ptr(), None, B, 25, 0, self.cam.ctypes.data, 0.0, float(w[0]), f.terms.ptr("kpts"), f.dJ.data_ptr(), st))
+        _chk(lib.vt_landmarks_backward(self.b25.h, f.dJ.data_ptr(), B, f.dverts.data_ptr(), 0, st))
+        if f.temporal:
+            _chk(lib.vt_accel_loss(f.verts.data_ptr(), B, 6890 * 3, None, float(w[1]), f.terms.ptr("temp"), f.dverts.data_ptr(), st))
+        self.smpl_backward(pose, f.betas, f.dverts, f.vposed, f.ws, f.scratch, f.dpose, f.dbetas, f.dtrans)
+        if f.temporal:
+            _chk(lib.vt_accel_loss_strided(pose.data_ptr(), B, 66, 156, self.jw66.data_ptr(), float(w[2]), f.terms.ptr("ptemp"), f.dpose.data_ptr(), st))
+        self.body_prior(pose, f.dpose, float(w[3]), f.terms, "pose", f.vb)
+        _chk(lib.vt_sqdiff_loss(pose.data_ptr() + 12, 156, f.pose_init.data_ptr() + 12, 156, B, 63, float(B * 63), float(w[4]),
+                                f.terms.ptr("pinit"), f.dpose.data_ptr() + 12, st))
+        f.adam.step()
+        _chk(lib.vt_loss_reduce_and_stop(f.terms.buf.data_ptr(), w.ctypes.data, len(f.terms.names), 1e-3, armed, f.loss_state.data_ptr(),
+                                         f.stop.data_ptr(), f.hist.data_ptr(), k, st))
 
-    def _smpl_tail(self, pose, pose_init, dpose, B, w, terms, names, adam, state, stop, hist, slot, ticket, armed):
+    def _human_query(self, f, k, w):
+        """the SMPL stage's SIF-Net query: df_h / part terms, their gradient written to dverts"""
+        ev = _ev_begin(f.lp)
+        _chk(_lib().vt_query_human_loss(self.net.h, C.byref(f.maps.c), f.verts.data_ptr(), f.crop_center.data_ptr(), f.body_center.data_ptr(), f.B, 6890,
+                                        self.labels.data_ptr(), f.vert_order_ptr, float(w[0]), float(w[1]), f.dverts.data_ptr(), f.terms.ptr("df_h"),
+                                        L.stream_ptr()))
+        _ev_end(f.lp, "human", ev, f.B, k)
+
+    def _smpl_step(self, f, phase, k, w, armed):
+        """one Adam step of the SMPL stage as single-purpose launches (forward_smpl + the loss of recon_fit_behave.py:452-513)"""
+        lib = _lib(); st = L.stream_ptr(); B = f.B; pose = f.pose
+        f.terms.zero(0, 6)
+        self.smpl_forward(pose, f.betas, f.trans, f.verts, f.jtr, f.vposed, f.ws)
+        self._human_query(f, k, w)
+        if phase == "kpts":
+            _chk(lib.vt_landmarks_forward(self.b25.h, f.verts.data_ptr(), B, f.J.data_ptr(), st))
+            _chk(lib.vt_kpts_loss(f.J.data_ptr(), f.body_kpts.data_ptr(), f.crop_center.data_ptr(), B, 25, 1, self.cam.ctypes.data, f.net_size,
+                                  float(w[4]), f.terms.ptr("j2d"), f.dJ.data_ptr(), st))
+            _chk(lib.vt_landmarks_backward(self.b25.h, f.dJ.data_ptr(), B, f.dverts.data_ptr(), 1, st))
+        if B >= 4:
+            _chk(lib.vt_accel_loss(f.verts.data_ptr(), B, 6890 * 3, None, float(w[5]), f.terms.ptr("stemp"), f.dverts.data_ptr(), st))
+        self.smpl_backward(pose, f.betas, f.dverts, f.vposed, f.ws, f.scratch, f.dpose, f.dbetas, f.dtrans)
+        self.body_prior(pose, f.dpose, float(w[2]), f.terms, "pose", f.vb)
+        # pinit = mean_B sum (pose[:, 3:72] - pose_init)^2
+        _chk(lib.vt_sqdiff_loss(pose.data_ptr() + 12, 156, f.pose_init.data_ptr() + 12, 156, B, 69, float(B), float(w[3]),
+                                f.terms.ptr("pinit"), f.dpose.data_ptr() + 12, st))
+        f.adam.step()
+        _chk(lib.vt_loss_reduce_and_stop(f.terms.buf.data_ptr(), w.ctypes.data, len(f.terms.names), 1e-3, armed, f.loss_state.data_ptr(),
+                                         f.stop.data_ptr(), f.hist.data_ptr(), k, st))
+
+    def _smpl_step_fused(self, f, phase, k, w, armed):
+        """``_smpl_step`` with the keypoint chain as one launch behind the query and one tail (the tail of the previous step left the terms zeroed)"""
+        lib = _lib(); st = L.stream_ptr(); B = f.B
+        self.smpl_forward(f.pose, f.betas, f.trans, f.verts, f.jtr, f.vposed, f.ws)
+        self._human_query(f, k, w)
+        if phase == "kpts":
+            # joints, 2-D keypoint term and its gradient ADDED to the query's (accumulate = 1: the float addition of vt_landmarks_backward) in one launch
+            _chk(lib.vt_kpts_step(self.b25.h, f.verts.data_ptr(), f.body_kpts.data_ptr(), f.crop_center.data_ptr(), B, 1, self.cam.ctypes.data, f.net_size,
+                                  float(w[4]), f.terms.ptr("j2d"), f.J.data_ptr(), f.dverts.data_ptr(), 1, st))
+        if B >= 4:
+            _chk(lib.vt_accel_loss(f.verts.data_ptr(), B, 6890 * 3, None, float(w[5]), f.terms.ptr("stemp"), f.dverts.data_ptr(), st))
+        self.smpl_backward(f.pose, f.betas, f.dverts, f.vposed, f.ws, f.scratch, f.dpose, f.dbetas, f.dtrans)
+        self._smpl_tail(f, k, w, armed)
+
+    def _smpl_step_fused_query(self, f, phase, k, w, armed):
+        """``_smpl_step_fused`` with the keypoint chain BEFORE the query and the query adding its gradient and the vertex acceleration stencil in its own
+        epilogue (vt_query_human_step: 8 launches per step with the two forward and three backward SMPL-H kernels and the tail)"""
+        lib = _lib(); st = L.stream_ptr(); B = f.B
+        self.smpl_forward(f.pose, f.betas, f.trans, f.verts, f.jtr, f.vposed, f.ws)
+        if phase == "kpts":
+            _chk(lib.vt_kpts_step(self.b25.h, f.verts.data_ptr(), f.body_kpts.data_ptr(), f.crop_center.data_ptr(), B, 1, self.cam.ctypes.data, f.net_size,
+                                  float(w[4]), f.terms.ptr("j2d"), f.J.data_ptr(), f.dverts.data_ptr(), 0, st))
+        ev = _ev_begin(f.lp)
+        _chk(lib.vt_query_human_step(self.net.h, C.byref(f.maps.c), f.verts.data_ptr(), f.crop_center.data_ptr(), f.body_center.data_ptr(), B, 6890,
+                                     self.labels.data_ptr(), f.vert_order_ptr, float(w[0]), float(w[1]), int(phase == "kpts"), float(w[5]),
+                                     f.terms.ptr("stemp") if B >= 4 else None, f.dverts.data_ptr(), f.terms.ptr("df_h"), st))
+        _ev_end(f.lp, "human", ev, B, k)
+        self.smpl_backward(f.pose, f.betas, f.dverts, f.vposed, f.ws, f.scratch, f.dpose, f.dbetas, f.dtrans)
+        self._smpl_tail(f, k, w, armed)
+
+    def _smpl_tail(self, f, k, w, armed):
         """body prior + pinit + Adam on every group + loss reduction / stop rule + term zeroing: one launch (vt_smplstep_tail)"""
-        adam.t += 1
-        sl = []
-        for k in range(3):
-            if k < len(adam.slices):
-                (p_, n_, g_, lr_), m_, v_ = adam.slices[k], adam.m[k], adam.v[k]
-                sl += [p_.data_ptr(), p_.shape[1], g_.data_ptr(), g_.shape[1], m_.data_ptr(), v_.data_ptr(), n_, lr_]
-            else:
-                sl += [None, 0, None, 0, None, None, 0, 0.0]
-        _chk(_lib().vt_smplstep_tail(pose.data_ptr(), pose_init.data_ptr(), dpose.data_ptr(), B, self.pri["body_mean"].data_ptr(), self.pri["body_prec"].data_ptr(),
-                                     float(w[2]) / B, terms.ptr("pose"), float(w[3]), terms.ptr("pinit"), *sl, adam.t, 0.9, 0.999, 1e-8,
-                                     terms.buf.data_ptr(), w.ctypes.data, len(names), 1e-3, armed, state.data_ptr(), stop.data_ptr(),
-                                     hist.data_ptr(), slot, ticket.data_ptr(), 6, L.stream_ptr()))
+        _chk(_lib().vt_smplstep_tail(f.pose.data_ptr(), f.pose_init.data_ptr(), f.dpose.data_ptr(), f.B, self.pri["body_mean"].data_ptr(),
+                                     self.pri["body_prec"].data_ptr(), float(w[2]) / f.B, f.terms.ptr("pose"), float(w[3]), f.terms.ptr("pinit"),
+                                     *f.adam.smpl_tail_groups, f.adam.tick(), 0.9, 0.999, 1e-8,
+                                     f.terms.buf.data_ptr(), w.ctypes.data, len(f.terms.names), 1e-3, armed, f.loss_state.data_ptr(), f.stop.data_ptr(),
+                                     f.hist.data_ptr(), k, f.ticket.data_ptr(), 6, L.stream_ptr()))
 
-    def _object_step_fused(self, phase, maps, nz, obj_R, obj_t, obj_s, crop_center, body_center, occ, sil, w, terms, names, adam, B, N, NV, R, X, dX, dR, dM, dt,
-                           Vt, dVt, img, fidx, sws, dimg, per, trans_init, smpl_verts, prof, state, stop, hist, k, ticket, armed, contact_box):
-        """one Adam step of the object stage as head -> (query | silhouette) -> stencils -> (contacts) -> tail; the arithmetic of the single-purpose
-        launches of _optimize_smpl_object in the same order"""
-        lib = _lib(); st = L.stream_ptr()
-        is_sil = phase == "sil"
-        svd_ws = getattr(R, "_vt_svd_ws", None)
-        svd_ptr = svd_ws.data_ptr() if svd_ws is not None else None
-        _chk(lib.vt_objstep_head(obj_R.data_ptr(), nz.data_ptr(), obj_t.data_ptr(), obj_s.data_ptr(), B, self.obj_points.data_ptr(), N, X.data_ptr(),
-                                 self.obj_verts.data_ptr() if is_sil else None, NV, Vt.data_ptr() if is_sil else None, R.data_ptr(), terms.buf.data_ptr(), 7, svd_ptr, st))
-        if not is_sil:
-            ev = _ev_begin(prof)
-            _chk(lib.vt_query_object_loss(self.net.h, C.byref(maps.c), X.data_ptr(), crop_center.data_ptr(), body_center.data_ptr(), B, N,
-                                          occ.data_ptr(), float(w[0]), dX.data_ptr(), terms.ptr("object"), st))
-            _ev_end(prof, "object", ev, B, k)
-        # phases 'object only' / 'sil': nothing adds to dX between the stencils and the tail, so the tail evaluates them itself (vt_objstep_tail_temporal: the same
-        # float additions in the same order, one launch less per step); phase 'joint' keeps the stencil launch (the contact term's additions come after it)
-        tail_temporal = B >= 4 and phase != "joint" and self.fused_tail_temporal
-        if B >= 4 and not tail_temporal:
-            _chk(lib.vt_temporal_loss2(X.data_ptr(), B, N * 3, float(w[1]), terms.ptr("otemp"), float(w[2]), terms.ptr("ovtemp"), dX.data_ptr(), int(is_sil), st))
-        elif is_sil and not tail_temporal:
+    def _object_query(self, f, k, w):
+        """the object stage's SIF-Net query: 'object' term, its gradient written to dX"""
+        ev = _ev_begin(f.lp)
+        _chk(_lib().vt_query_object_loss(self.net.h, C.byref(f.maps.c), f.X.data_ptr(), f.crop_center.data_ptr(), f.body_center.data_ptr(), f.B, f.N,
+                                         f.occ.data_ptr(), float(w[0]), f.dX.data_ptr(), f.terms.ptr("object"), L.stream_ptr()))
+        _ev_end(f.lp, "object", ev, f.B, k)
+
+    def _contacts(self, f, w):
+        """the contact term of a 'joint' step; the first one computes the contact set"""
+        if f.contact is None:
+            f.contact = self._contacts_once(f.maps, f.smpl_verts, f.X, f.crop_center, f.body_center)
+        if f.contact["P"] > 0:
+            self._contact_term(f.contact, f.X, f.dX, float(w[5]), f.terms)
+
+    def _object_step(self, f, phase, k, w, armed):
+        """one Adam step of the object stage as single-purpose launches (forward_step + the loss of recon_fit_trivis_full.py:193-283): the reference of
+        the fused step, and the step of phase 'joint' with the interpenetration term"""
+        lib = _lib(); st = L.stream_ptr(); B, N, NV, nz = f.B, f.N, f.NV, f.noise[k]
+        obj_R, obj_t, obj_s, X, dX, R, dR, dt = f.obj_R, f.obj_t, f.obj_s, f.X, f.dX, f.R, f.dR, f.dt
+        nf = self.obj_faces.shape[0]
+        f.terms.zero(0, 7)
+        _chk(lib.vt_so3_project_forward(obj_R.data_ptr(), nz.data_ptr(), B, R.data_ptr(), st))
+        _chk(lib.vt_rigid_forward(self.obj_points.data_ptr(), 1, R.data_ptr(), obj_t.data_ptr(), obj_s.data_ptr(), B, N, X.data_ptr(), st))
+        if phase == "sil":
             _chk(lib.vt_fill(dX.data_ptr(), dX.numel(), 0.0, st))
-        if is_sil and self.fused_sil_step:
-            # the silhouette term of the step in 5 launches (vt_sil_step) instead of the 10 of the three calls below: same arithmetic, bit-identical gradients
-            _chk(lib.vt_sil_step(Vt.data_ptr(), B, NV, self.obj_faces.data_ptr(), self.obj_faces.shape[0], sil.K.data_ptr(), sil.size, sil.keep.data_ptr(),
-                                 sil.ref.data_ptr(), occ.data_ptr(), float(w[3]), 1e-4, terms.ptr("mask"), fidx.data_ptr(), dimg.data_ptr(), sws.data_ptr(),
-                                 dVt.data_ptr(), st))
-        elif is_sil:
-            _chk(lib.vt_sil_forward(Vt.data_ptr(), B, NV, self.obj_faces.data_ptr(), self.obj_faces.shape[0], sil.K.data_ptr(), sil.size,
-                                    img.data_ptr(), fidx.data_ptr(), sws.data_ptr(), st))
-            _chk(lib.vt_sil_mask_loss(img.data_ptr(), sil.keep.data_ptr(), sil.ref.data_ptr(), occ.data_ptr(), B, sil.size, float(w[3]),
-                                      terms.ptr("mask"), per.data_ptr(), dimg.data_ptr(), st))
-            _chk(lib.vt_sil_backward(Vt.data_ptr(), B, NV, self.obj_faces.data_ptr(), self.obj_faces.shape[0], sil.K.data_ptr(), sil.size,
-                                     fidx.data_ptr(), dimg.data_ptr(), 1e-4, sws.data_ptr(), dVt.data_ptr(), st))
-        if phase == "joint":
-            if contact_box[0] is None:
-                contact_box[0] = self._contacts_once(maps, smpl_verts, X, crop_center, body_center)
-            contact = contact_box[0]
-            if contact["P"] > 0:
-                self._contact_term(contact, X, dX, float(w[5]), terms)
-        adam.t += 1
-        gR = gT = (None, None, None, 0.0)
-        for (p_, n_, g_, lr_), m_, v_ in zip(adam.slices, adam.m, adam.v):
-            if n_ == 9:
-                gR = (p_.data_ptr(), m_.data_ptr(), v_.data_ptr(), lr_)
-            else:
-                gT = (p_.data_ptr(), m_.data_ptr(), v_.data_ptr(), lr_)
-        tail_args = (self.obj_verts.data_ptr() if is_sil else None, NV, dVt.data_ptr() if is_sil else None, self.obj_points.data_ptr(), N, dX.data_ptr(),
-                     obj_s.data_ptr(), B, obj_R.data_ptr(), nz.data_ptr(), obj_t.data_ptr(), trans_init.data_ptr() if is_sil else None, float(w[4]),
-                     terms.ptr("trans"), dR.data_ptr(), dt.data_ptr(), dM.data_ptr(), *gR, *gT, adam.t, 0.9, 0.999, 1e-8,
-                     terms.buf.data_ptr(), w.ctypes.data, len(names), 1e-4, armed, state.data_ptr(), stop.data_ptr(), hist.data_ptr(), k, ticket.data_ptr(), 0, svd_ptr, st)
-        if tail_temporal:
-            _chk(lib.vt_objstep_tail_temporal(X.data_ptr(), float(w[1]), terms.ptr("otemp"), float(w[2]), terms.ptr("ovtemp"), int(is_sil), *tail_args))
         else:
-            _chk(lib.vt_objstep_tail(*tail_args))
+            self._object_query(f, k, w)
+        if B >= 4:
+            _chk(lib.vt_accel_loss(X.data_ptr(), B, N * 3, None, float(w[1]), f.terms.ptr("otemp"), dX.data_ptr(), st))
+            _chk(lib.vt_velocity_loss(X.data_ptr(), B, N * 3, float(w[2]), f.terms.ptr("ovtemp"), dX.data_ptr(), st))
+        acc = 0
+        if phase == "sil":
+            sil = f.sil
+            _chk(lib.vt_rigid_forward(self.obj_verts.data_ptr(), 1, R.data_ptr(), obj_t.data_ptr(), obj_s.data_ptr(), B, NV, f.Vt.data_ptr(), st))
+            _chk(lib.vt_sil_forward(f.Vt.data_ptr(), B, NV, self.obj_faces.data_ptr(), nf, sil.K.data_ptr(), sil.size, f.img.data_ptr(), f.fidx.data_ptr(),
+                                    f.sws.data_ptr(), st))
+            _chk(lib.vt_sil_mask_loss(f.img.data_ptr(), sil.keep.data_ptr(), sil.ref.data_ptr(), f.occ.data_ptr(), B, sil.size, float(w[3]),
+                                      f.terms.ptr("mask"), f.per.data_ptr(), f.dimg.data_ptr(), st))
+            _chk(lib.vt_sil_backward(f.Vt.data_ptr(), B, NV, self.obj_faces.data_ptr(), nf, sil.K.data_ptr(), sil.size, f.fidx.data_ptr(), f.dimg.data_ptr(),
+                                     1e-4, f.sws.data_ptr(), f.dVt.data_ptr(), st))
+            _chk(lib.vt_rigid_backward(self.obj_verts.data_ptr(), 1, obj_s.data_ptr(), B, NV, f.dVt.data_ptr(), dR.data_ptr(), dt.data_ptr(), 0, st))
+            _chk(lib.vt_sqdiff_loss(obj_t.data_ptr(), 3, f.trans_init.data_ptr(), 3, B, 3, float(B * 3), float(w[4]), f.terms.ptr("trans"), dt.data_ptr(), st))
+            acc = 1
+        if phase == "joint":
+            self._contacts(f, w)
+        _chk(lib.vt_rigid_backward(self.obj_points.data_ptr(), 1, obj_s.data_ptr(), B, N, dX.data_ptr(), dR.data_ptr(), dt.data_ptr(), acc, st))
+        if phase == "joint" and self.collision_loss:
+            # prevent interpenetration (recon_fit_trivis_full.py:260-264): SMPL mesh vs the transformed object template
+            if f.cws is None:
+                f.Vc = torch.empty(B, NV, 3, device=X.device)
+                f.cws = torch.empty((lib.vt_collision_workspace_bytes(B, self.smpl_faces.shape[0]) + 7) // 8, dtype=torch.int64, device=X.device)
+            _chk(lib.vt_rigid_forward(self.obj_verts.data_ptr(), 1, R.data_ptr(), obj_t.data_ptr(), obj_s.data_ptr(), B, NV, f.Vc.data_ptr(), st))
+            _chk(lib.vt_collision_loss(f.smpl_verts.data_ptr(), f.smpl_verts.shape[1], self.smpl_faces.data_ptr(), self.smpl_faces.shape[0], f.Vc.data_ptr(), NV,
+                                       self.obj_faces.data_ptr(), nf, B, 0.5, 8, float(w[6]), f.terms.ptr("collide"), dt.data_ptr(), None, f.cws.data_ptr(), st))
+        _chk(lib.vt_so3_project_backward(obj_R.data_ptr(), nz.data_ptr(), B, dR.data_ptr(), f.dM.data_ptr(), st))
+        f.adam.step()
+        _chk(lib.vt_loss_reduce_and_stop(f.terms.buf.data_ptr(), w.ctypes.data, len(f.terms.names), 1e-4, armed, f.loss_state.data_ptr(), f.stop.data_ptr(),
+                                         f.hist.data_ptr(), k, st))
+
+    def _object_step_fused(self, f, phase, k, w, armed):
+        """one Adam step of the object stage as head -> (query | silhouette) -> stencils -> (contacts) -> tail; the arithmetic of ``_object_step`` in
+        the same order.  The head leaves its SVD of M0 + noise in ``f.svd_ws`` for the tail of the same step."""
+        lib = _lib(); st = L.stream_ptr(); B, N, NV, nz = f.B, f.N, f.NV, f.noise[k]
+        is_sil = phase == "sil"
+        X, dX = f.X.data_ptr(), f.dX.data_ptr()
+        obj_verts, Vt, dVt = (self.obj_verts.data_ptr(), f.Vt.data_ptr(), f.dVt.data_ptr()) if is_sil else (None, None, None)
+        _chk(lib.vt_objstep_head(f.obj_R.data_ptr(), nz.data_ptr(), f.obj_t.data_ptr(), f.obj_s.data_ptr(), B, self.obj_points.data_ptr(), N, X,
+                                 obj_verts, NV, Vt, f.R.data_ptr(), f.terms.buf.data_ptr(), 7, f.svd_ws.data_ptr(), st))
+        if not is_sil:
+            self._object_query(f, k, w)
+        # phases 'object only' / 'sil': nothing adds to dX between the temporal stencils and the tail, so the tail evaluates them itself
+        # (vt_objstep_tail_temporal); phase 'joint' keeps the stencil launch (the contact term's additions come after it)
+        tail_temporal = B >= 4 and phase != "joint"
+        if B >= 4 and phase == "joint":
+            _chk(lib.vt_temporal_loss2(X, B, N * 3, float(w[1]), f.terms.ptr("otemp"), float(w[2]), f.terms.ptr("ovtemp"), dX, 0, st))
+        elif is_sil and B < 4:
+            _chk(lib.vt_fill(dX, f.dX.numel(), 0.0, st))
+        if is_sil:
+            # the silhouette term in 5 launches: vt_sil_forward + vt_sil_mask_loss + vt_sil_backward, bit-identical gradients
+            sil = f.sil
+            _chk(lib.vt_sil_step(Vt, B, NV, self.obj_faces.data_ptr(), self.obj_faces.shape[0], sil.K.data_ptr(), sil.size, sil.keep.data_ptr(),
+                                 sil.ref.data_ptr(), f.occ.data_ptr(), float(w[3]), 1e-4, f.terms.ptr("mask"), f.fidx.data_ptr(), f.dimg.data_ptr(),
+                                 f.sws.data_ptr(), dVt, st))
+        if phase == "joint":
+            self._contacts(f, w)
+        tail, pre = lib.vt_objstep_tail, ()
+        if tail_temporal:
+            tail, pre = lib.vt_objstep_tail_temporal, (X, float(w[1]), f.terms.ptr("otemp"), float(w[2]), f.terms.ptr("ovtemp"), int(is_sil))
+        _chk(tail(*pre, obj_verts, NV, dVt, self.obj_points.data_ptr(), N, dX, f.obj_s.data_ptr(), B, f.obj_R.data_ptr(), nz.data_ptr(), f.obj_t.data_ptr(),
+                  f.trans_init.data_ptr() if is_sil else None, float(w[4]), f.terms.ptr("trans"), f.dR.data_ptr(), f.dt.data_ptr(), f.dM.data_ptr(),
+                  *f.adam.object_tail_groups, f.adam.tick(), 0.9, 0.999, 1e-8, f.terms.buf.data_ptr(), w.ctypes.data, len(f.terms.names), 1e-4, armed,
+                  f.loss_state.data_ptr(), f.stop.data_ptr(), f.hist.data_ptr(), k, f.ticket.data_ptr(), 0, f.svd_ws.data_ptr(), st))
 
     def _contact_term(self, contact, X, dX, w, terms):
         """the contact Chamfer term of a 'joint' step (recon_fit_trivis_full.py:449-457): the object-side contact points are read out of X and their gradient
