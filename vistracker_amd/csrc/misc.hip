@@ -990,8 +990,13 @@ __device__ __forceinline__ void adam_one(const AdamSlice &a, int b, int c, float
     const float denom = sqrtf(vi) / bc2s + eps;
     a.p[(size_t)b * a.pstride + c] = a.p[(size_t)b * a.pstride + c] - a.step_size * (mi / denom);
 }
+// the fence-free step end below leans on how gfx942 / gfx950 perform fp64 atomics and count them in vmcnt: any other target gets the fenced form
 #ifndef STEP_END_FENCE
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx942__) && !defined(__gfx950__)
+#define STEP_END_FENCE 1
+#else
 #define STEP_END_FENCE 0
+#endif
 #endif
 // the workgroup that takes the last ticket closes the step: weighted loss, history, the reference's stop rule (loss_reduce_kernel), and the term
 // accumulators [0, nzero) zeroed for the next step.  Every other workgroup has finished (its writes fenced) by then.
@@ -1290,6 +1295,9 @@ extern "C" int vt_smplstep_tail(float *pose, const float *pose_init, float *dpos
 {
     VT_REQUIRE(pose && pose_init && dpose && prior_mean && prior_prec && term_prior && term_pinit && B > 0 && adam_step >= 1, "vt_smplstep_tail: bad argument");
     VT_REQUIRE(terms && w && state && ticket && nterms > 0 && nterms <= 16 && nzero >= 0 && nzero <= nterms, "vt_smplstep_tail: bad loss arguments");
+    // a group that is optimised needs its gradient and both moments (the kernel would follow a NULL pointer otherwise), and strides that hold its columns
+    VT_REQUIRE((!p0 || (g0 && m0 && v0 && n0 > 0 && ps0 >= n0 && gs0 >= n0)) && (!p1 || (g1 && m1 && v1 && n1 > 0 && ps1 >= n1 && gs1 >= n1)) &&
+               (!p2 || (g2 && m2 && v2 && n2 > 0 && ps2 >= n2 && gs2 >= n2)), "vt_smplstep_tail: a parameter group without its gradient / moments, or a stride below its column count");
     const double bc1 = 1.0 - pow((double)beta1, adam_step), bc2 = 1.0 - pow((double)beta2, adam_step);
     AdamSlice a0 = {p0, ps0, g0, gs0, m0, v0, n0, (float)(lr0 / bc1)}, a1 = {p1, ps1, g1, gs1, m1, v1, n1, (float)(lr1 / bc1)}, a2 = {p2, ps2, g2, gs2, m2, v2, n2, (float)(lr2 / bc1)};
     hipLaunchKernelGGL(smplstep_tail_kernel, dim3(B), dim3(64), 0, vt_stream(stream), pose, pose_init, dpose, prior_mean, prior_prec, gscale_prior, term_prior, w_pinit, term_pinit,
