@@ -1,6 +1,6 @@
-"""Test helper (not a test file): the operations of the fused Adam-step kernels of csrc/misc.hip restated in float64 numpy.
+"""Test helper (not a test file): the operations of the Adam-step kernels (csrc/step.hip, csrc/misc.hip; stated once in csrc/step_ops.h) restated in float64 numpy.
 
-Written from the contract comments of misc.hip and DESIGN.md 4.5, not from the kernels' loops: every sum is ``np.sum``, the SVD is
+Written from the contract comments of step_ops.h / step.hip and DESIGN.md 4.5, not from the kernels' loops: every sum is ``np.sum``, the SVD is
 ``np.linalg.svd``, the stencils are array slices.  Nothing here touches libvistracker_hip.so.
 
 Every function takes ``fp32=True`` to evaluate the SAME expression in float32 numpy.  That switch exists to size tolerances only: the distance
@@ -55,7 +55,7 @@ def so3_margin(M0, noise=None):
 
 
 def so3_vjp_polar(M0, noise, G, fp32=False):
-    """VJP of project_so3 in polar form (header of the SO(3) section of misc.hip): dM = U D Z V^T, Q = D U^T G V, Z_ij = (Q_ij - Q_ji) / (h_i + h_j)"""
+    """VJP of project_so3 in polar form (header of the SO(3) section of step_ops.h): dM = U D Z V^T, Q = D U^T G V, Z_ij = (Q_ij - Q_ji) / (h_i + h_j)"""
     p = project_so3(M0, noise, fp32)
     U, V, h = p["U"], p["V"], p["h"]
     G = _c(G, fp32).reshape(-1, 3, 3)

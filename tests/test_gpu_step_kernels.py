@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the fused Adam-step kernels of csrc/misc.hip, each called through the C ABI and compared, buffer by buffer, with the float64 model of
+"""GPU (-m gpu): the fused Adam-step kernels of csrc/step.hip and the single-purpose ones of csrc/misc.hip, each called through the C ABI and compared, buffer by buffer, with the float64 model of
 its operation (tests/step_model.py).  Buffers the contract leaves alone start from a sentinel and are compared bit for bit.
 
 Tolerances: the bar test_gpu_parity.py holds the same operation to is the floor (rigid 1e-5 abs / 1e-4 rel on gradients, SO(3) 3e-6 / 2e-4, stencils and
