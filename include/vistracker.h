@@ -544,6 +544,31 @@ int vt_render_rgb(const float *verts, int B, int NV, const int *faces, int NF, c
                   int *face_index, void *ws, long ws_bytes, long *list_entries, void *stream);
 int vt_render_panel_u8(const float *rgb, int B, int size, int row0, int nrows, int col0, int ncols, unsigned char *out, const long long *view_off,
                        long long out_row_stride, void *stream);
+/* vt_render_rgb_pv: vt_render_rgb with face_colors (B,NF,3), one table per view, when colors_per_view != 0 (render/nr_utils.py:527-535: with
+ *   contact_viz_type 'face' the object's colours depend on the frame); with colors_per_view == 0 it IS vt_render_rgb, which forwards here. */
+int vt_render_rgb_pv(const float *verts, int B, int NV, const int *faces, int NF, const float *face_colors, int colors_per_view, const float *K, int k_per_view,
+                     float orig_size, const float *light, const float *background, const void *static_layer, int size, int anti_aliasing, float *rgb,
+                     float *alpha, float *depth, int *face_index, void *ws, long ws_bytes, long *list_entries, void *stream);
+
+/* ---- contacts between body and object (demo.sh step 7 with viz_contact: render/nr_utils.py:380-404 ContactVisualizer.get_contact_spheres, :100-122
+ * color_contact_faces / color_contact_faces_all, :504-535 NrWrapper.prepare_render) ------------------------------------------------------------------------
+ * The reference queries a scipy cKDTree of the SMPL vertices with the object's vertices, per frame, on the host; here: brute force on the device, B frames a
+ * call, no float atomics, results bit-identical from run to run and independent of B and of a frame's place in the batch (contact.hip's header).
+ * PARITY UNPINNED: psbody.mesh.sphere.Sphere.to_mesh is not installed; the sphere tessellation is this project's icosphere (visualize.icosphere).
+ *
+ * vt_contact_regions: smpl_verts (B,NVs,3), labels (NVs) int32 in [0,P) (P <= 32; nr_utils.py:367-372), obj_verts (B,NVo,3), thres (nr_utils.py:384, 0.04 in
+ *   NrWrapper) -> nn_idx (B,NVo) int32 nearest SMPL vertex on the squared fp32 distance, exact ties to the smaller index; nn_dist (B,NVo) its sqrtf; part (B,NVo)
+ *   int32 labels[nn_idx] where nn_dist < thres, else -1; count (B,P) int32; centre (B,P,3) mean of the object vertices of the part (nr_utils.py:398-399),
+ *   accumulated in fp64 in a fixed order and rounded once, 0 where count == 0.
+ * vt_contact_spheres: unit_verts (NSV,3) sphere template -> out (B, P NSV, 3): centre + radius * unit per (frame, part) (nr_utils.py:400), every vertex at the
+ *   centre (0) where count == 0: such faces have three identical corners and are culled by vt_render_rgb's set-up (zero area) before binning.
+ * vt_contact_face_colors: out (B,NF,3) = base_colors (NF,3), except faces face_off + g, g < NFo, of the object (obj_faces (NFo,3) int32 into its NVo vertices) with
+ *   a corner in contact: palette[highest part among the corners] (nr_utils.py:114-122: parts in ascending order, each overwriting).  Feeds vt_render_rgb_pv. */
+int vt_contact_regions(const float *smpl_verts, const int *labels, const float *obj_verts, int B, int NVs, int NVo, int P, float thres, int *nn_idx,
+                       float *nn_dist, int *part, int *count, float *centre, void *stream);
+int vt_contact_spheres(const float *centre, const int *count, int B, int P, const float *unit_verts, int NSV, float radius, float *out, void *stream);
+int vt_contact_face_colors(const int *part, int B, int NVo, const int *obj_faces, int NFo, int face_off, const float *base_colors, int NF, const float *palette,
+                           int P, float *out, void *stream);
 
 /* ---- Motion-JPEG video of demo step 7 (render/render_side_comp.py:71-72 drives render/render_recon.py, which appends every frame to an imageio FFMPEG
  * writer: render_recon.py:113-115 imageio.get_writer(..., format='FFMPEG', fps), :169 and :188 writer.append_data(frame)) --------------------------------

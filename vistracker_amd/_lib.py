@@ -132,6 +132,11 @@ SIGNATURES = {
     "vt_render_rgb": (ci, [fp, ci, ci, fp, ci, fp, fp, ci, cf, C.POINTER(cf), C.POINTER(cf), vp, ci, ci, fp, fp, fp, fp, fp, cl,
                            C.POINTER(cl), vp]),
     "vt_render_panel_u8": (ci, [fp, ci, ci, ci, ci, ci, ci, fp, fp, C.c_longlong, vp]),
+    "vt_render_rgb_pv": (ci, [fp, ci, ci, fp, ci, fp, ci, fp, ci, cf, C.POINTER(cf), C.POINTER(cf), vp, ci, ci, fp, fp, fp, fp, fp, cl,
+                              C.POINTER(cl), vp]),
+    "vt_contact_regions": (ci, [fp, fp, fp, ci, ci, ci, ci, cf, fp, fp, fp, fp, fp, vp]),
+    "vt_contact_spheres": (ci, [fp, fp, ci, ci, fp, ci, cf, fp, vp]),
+    "vt_contact_face_colors": (ci, [fp, ci, ci, fp, ci, ci, fp, ci, fp, ci, fp, vp]),
     "vt_jpeg_workspace_bytes": (cl, [ci, ci, ci, ci, C.POINTER(C.c_longlong)]),
     "vt_jpeg_encode": (ci, [fp, ci, ci, ci, C.c_longlong, C.c_longlong, ci, ci, vp, cl, vp, C.c_longlong,
                             C.POINTER(C.c_longlong), vp]),

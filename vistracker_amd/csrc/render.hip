@@ -102,7 +102,7 @@ __device__ __forceinline__ int2 rnd_box(const float (&fc)[9], int is)
 __device__ __forceinline__ bool rnd_box_ok(int2 bb) { return (bb.x & 0xffff) <= (bb.x >> 16); }
 
 __global__ __launch_bounds__(256) void rnd_setup_kernel(const float *__restrict__ verts, int NV, const int *__restrict__ faces, int NF,
-                                                       const float *__restrict__ colors, const float *__restrict__ K, int k_stride, float os, int is,
+                                                       const float *__restrict__ colors, long c_stride, const float *__restrict__ K, int k_stride, float os, int is,
                                                        RndLight L, int idA, int idB, float4 *__restrict__ rec, int2 *__restrict__ box)
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void rnd_setup_kernel(const float *__restrict_
     for (int e = 0; e < 3; e++) {
         float l = 0.f + L.ia * L.ca[e];
         l = l + L.id * (L.cd[e] * cs);
-        rgb[e] = colors[3 * f + e] * l;
+        rgb[e] = colors[c_stride * b + 3 * f + e] * l;
     }
     const int id = useB ? idB + f : idA + f;
     float4 *r = rec + ((size_t)b * NF + f) * 4;
@@ -340,11 +340,11 @@ static inline RndLight rnd_light(const float *l)
 }
 // set-up + binning of B views of an NF-face scene; returns the list length through *total_host (the one host synchronisation of a call: the
 // caller's workspace must hold the list)
-static int rnd_bin(const float *verts, int B, int NV, const int *faces, int NF, const float *colors, const float *K, int k_stride, float os, int is,
+static int rnd_bin(const float *verts, int B, int NV, const int *faces, int NF, const float *colors, long c_stride, const float *K, int k_stride, float os, int is,
                    const RndLight &L, int idA, int idB, const RndWs &w, long long *total_host, hipStream_t st)
 {
     const int tiles_x = is / RND_TILE, n = B * tiles_x * tiles_x;
-    hipLaunchKernelGGL(rnd_setup_kernel, dim3((NF + 255) / 256, B), dim3(256), 0, st, verts, NV, faces, NF, colors, K, k_stride, os, is, L, idA, idB, w.rec, w.box);
+    hipLaunchKernelGGL(rnd_setup_kernel, dim3((NF + 255) / 256, B), dim3(256), 0, st, verts, NV, faces, NF, colors, c_stride, K, k_stride, os, is, L, idA, idB, w.rec, w.box);
     VT_LAUNCH_CHECK();
     VT_HIP(hipMemsetAsync(w.cnt, 0, sizeof(int) * (size_t)n, st));
     hipLaunchKernelGGL(rnd_count_kernel, dim3((NF + 255) / 256, B), dim3(256), 0, st, w.box, NF, tiles_x, w.cnt);
@@ -382,7 +382,7 @@ extern "C" int vt_render_static_create(void **out, const float *verts, int NV, c
         if (hipMalloc(&ws, bytes) != hipSuccess) { rc = VT_ERR_HIP; snprintf(vt_err_buf, sizeof(vt_err_buf), "vt_render_static_create: hipMalloc(%ld) failed", bytes); break; }
         const RndWs w = rnd_ws(ws, bytes, 1, NS, is);
         long long total = 0;
-        rc = rnd_bin(verts, 1, NV, faces, NS, face_colors, K, 0, orig_size, is, L, 0, NS, w, &total, st);
+        rc = rnd_bin(verts, 1, NV, faces, NS, face_colors, 0, K, 0, orig_size, is, L, 0, NS, w, &total, st);
         if (rc != VT_OK) break;
         if (total > w.cap) { (void)hipFree(ws); ws = nullptr; entries = total; continue; }   // exact size known now: one retry
         if (hipMalloc(&h->rec, sizeof(float4) * 4 * (size_t)NS) != hipSuccess || hipMalloc(&h->keys, sizeof(unsigned long long) * (size_t)is * is) != hipSuccess) {
@@ -417,9 +417,11 @@ extern "C" void vt_render_static_destroy(void *layer)
     delete h;
 }
 
-extern "C" int vt_render_rgb(const float *verts, int B, int NV, const int *faces, int NF, const float *face_colors, const float *K, int k_per_view,
-                             float orig_size, const float *light, const float *background, const void *static_layer, int size, int anti_aliasing,
-                             float *rgb, float *alpha, float *depth, int *face_index, void *ws, long ws_bytes, long *list_entries, void *stream)
+// face_colors (NF,3) shared by the views, or (B,NF,3) with colors_per_view (contact-coloured object faces differ from view to view: nr_utils.py:527-535)
+extern "C" int vt_render_rgb_pv(const float *verts, int B, int NV, const int *faces, int NF, const float *face_colors, int colors_per_view, const float *K,
+                                int k_per_view, float orig_size, const float *light, const float *background, const void *static_layer, int size,
+                                int anti_aliasing, float *rgb, float *alpha, float *depth, int *face_index, void *ws, long ws_bytes, long *list_entries,
+                                void *stream)
 {
     VT_REQUIRE(verts && faces && face_colors && K && light && background && rgb && alpha && ws && B > 0 && NV > 0 && NF > 0 && size > 0 && orig_size > 0.f,
                "vt_render_rgb: bad argument");
@@ -434,7 +436,7 @@ extern "C" int vt_render_rgb(const float *verts, int B, int NV, const int *faces
     const RndLight L = rnd_light(light);
     const int NS = sl ? sl->NS : 0;
     long long total = 0;
-    const int rc = rnd_bin(verts, B, NV, faces, NF, face_colors, K, k_per_view ? 9 : 0, orig_size, is, L, 0, NF + NS, w, &total, st);
+    const int rc = rnd_bin(verts, B, NV, faces, NF, face_colors, colors_per_view ? 3L * NF : 0L, K, k_per_view ? 9 : 0, orig_size, is, L, 0, NF + NS, w, &total, st);
     if (rc != VT_OK) return rc;
     if (list_entries) *list_entries = (long)total;
     if (total > w.cap) VT_FAIL(VT_ERR_ARG, "vt_render_rgb: workspace holds %lld tile-list entries, this batch needs %lld (vt_render_workspace_bytes)", w.cap, total);
@@ -455,4 +457,12 @@ extern "C" int vt_render_panel_u8(const float *rgb, int B, int size, int row0, i
     hipLaunchKernelGGL(rnd_panel_kernel, dim3((3 * ncols + 255) / 256, nrows, B), dim3(256), 0, st, rgb, size, row0, nrows, col0, ncols, out, view_off, out_row_stride);
     VT_LAUNCH_CHECK();
     return VT_OK;
+}
+
+extern "C" int vt_render_rgb(const float *verts, int B, int NV, const int *faces, int NF, const float *face_colors, const float *K, int k_per_view,
+                             float orig_size, const float *light, const float *background, const void *static_layer, int size, int anti_aliasing,
+                             float *rgb, float *alpha, float *depth, int *face_index, void *ws, long ws_bytes, long *list_entries, void *stream)
+{
+    return vt_render_rgb_pv(verts, B, NV, faces, NF, face_colors, 0, K, k_per_view, orig_size, light, background, static_layer, size, anti_aliasing, rgb, alpha,
+                            depth, face_index, ws, ws_bytes, list_entries, stream);
 }

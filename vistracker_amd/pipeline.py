@@ -18,6 +18,7 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from types import SimpleNamespace
 
+import os
 import time
 
 import numpy as np
@@ -341,21 +342,58 @@ class SequencePipeline:
         return out
 
     def render(self, out, kin, rgb=None, template=None, outdir=None, start=0, end=None, interval=1, chunk=8, image_size=1200,
-               video=None, fps=30, quality=90):
+               video=None, fps=30, quality=90, viz_contact=False, contact_viz_type='sphere', add_top=False):
         """demo step 7 (render/render_side_comp.py -s1 <recon>) on ``out["recon"]`` of ``run``: side-by-side frames [input rgb | camera 1 | camera 2]
         of the fitted SMPL-H body and object on the checkerboard ground (visualize.RendererSide2side).  ``kin``: visualize.KinectTransform of the
         sequence; ``template``: (verts, faces) of the object template; ``rgb``: None, a sequence or a callable frame index -> camera-1 image.  With
         ``outdir`` the frames are written there (PNG) and their paths returned; with ``video`` (a path) they go, without leaving the device, into a
         Motion-JPEG AVI at ``fps`` (render_recon.py -fps, 30) and JPEG ``quality`` (video.write_video) and the path is returned; otherwise the
-        generator of uint8 frame chunks is."""
+        generator of uint8 frame chunks is.
+
+        ``viz_contact`` marks where the body touches the object: one sphere per touching body part (``contact_viz_type='sphere'``) or the touched
+        object faces recoloured (``'face'``).  ``add_top`` (render_side_comp.py -add_top) adds the top-down strips [rgb | top view]: they go to
+        ``<outdir>/top_*.png`` or ``<video stem>_top.avi`` and the call returns both results as a pair (frames, top); without ``outdir`` and
+        ``video`` the generator yields (frames, top_frames) chunk pairs."""
         from . import visualize
         if template is None:
             raise ValueError("render() needs the object template (verts, faces)")
-        r = visualize.RendererSide2side(image_size=image_size, device=self.device)
+        r = visualize.RendererSide2side(image_size=image_size, device=self.device, contact_viz_type=contact_viz_type,
+                                        part_labels=self.ctx.labels if viz_contact else None)
+        gen = r.render_frames([out["recon"]], template[0], template[1], self.ctx.smpl, kin, rgb=rgb, start=start, end=end, interval=interval, chunk=chunk,
+                              on_device=video is not None, viz_contact=viz_contact, add_top=add_top)
         if video is not None:
             from . import video as vid
-            gen = r.render_frames([out["recon"]], template[0], template[1], self.ctx.smpl, kin, rgb=rgb, start=start, end=end, interval=interval, chunk=chunk,
-                                  on_device=True)
-            return vid.write_video(gen, video, fps=fps, quality=quality)[0]
-        gen = r.render_frames([out["recon"]], template[0], template[1], self.ctx.smpl, kin, rgb=rgb, start=start, end=end, interval=interval, chunk=chunk)
-        return visualize.write_frames(gen, outdir, start=start) if outdir is not None else gen
+            if not add_top:
+                return vid.write_video(gen, video, fps=fps, quality=quality)[0]
+            stem, ext = os.path.splitext(video)
+            return tuple(p for p, _ in vid.write_videos(gen, [video, stem + "_top" + ext], fps=fps, quality=quality))
+        if outdir is None:
+            return gen
+        if not add_top:
+            return visualize.write_frames(gen, outdir, start=start)
+        paths, tops = [], []
+        for fr, top in gen:
+            paths += visualize.write_frames([fr], outdir, start=start + len(paths))
+            tops += visualize.write_frames([top], outdir, start=start + len(tops), prefix="top")
+        return paths, tops
+
+    def contacts(self, out, template, chunk=64):
+        """Which body part touches the object in which frame of ``out["recon"]`` (visualize.ContactVisualizer.regions at the renderer's threshold of
+        0.04 m, no rendering): {"count": (T,14) int32 object vertices in contact per part, "centre": (T,14,3) float32 their mean (0 where none),
+        "part": (T,NVo) int32 part of every object vertex or -1}.  ``template``: (verts, faces) of the object template."""
+        from . import ops, visualize
+        d = out["recon"]
+        dev = torch.device(self.device)
+        cv = visualize.ContactVisualizer(self.ctx.labels, thres=0.04, radius=0.06, device=dev)
+        T = len(d["poses"])
+        tv = torch.as_tensor(np.asarray(template[0]), dtype=torch.float32, device=dev)
+        res = {"count": [], "centre": [], "part": []}
+        with torch.cuda.device(dev):
+            for c0 in range(0, T, chunk):
+                g = lambda k, w: torch.as_tensor(np.asarray(d[k], np.float32).reshape(T, w)[c0:c0 + chunk], device=dev).contiguous()
+                sv, _, _ = ops.smplh_forward(self.ctx.smpl, g("poses", 156), g("betas", 10), g("trans", 3))
+                ov = (tv[None] @ g("obj_angles", 9).reshape(-1, 3, 3) + g("obj_trans", 3)[:, None]) * g("obj_scales", 1)[:, :, None]
+                reg = cv.regions(sv.detach(), ov)
+                for k in res:
+                    res[k].append(reg[k].cpu().numpy())
+        return {k: np.concatenate(v) for k, v in res.items()}

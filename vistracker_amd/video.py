@@ -275,3 +275,37 @@ def write_video(chunks, path, fps=30, quality=90, subsampling="420", device=None
         if writer is not None:
             writer.close()
     return path, count
+
+
+def write_videos(chunk_tuples, paths, fps=30, quality=90, subsampling="420", device=None):
+    """``write_video`` for k videos fed together: ``chunk_tuples`` yields k-tuples of frame chunks, chunk j of every tuple goes to ``paths[j]`` (sizes may
+    differ from video to video), so no video's frames have to be kept while another is written -> list of (path, frame count)"""
+    _check_quality(quality); _check_subsampling(subsampling)
+    k = len(paths)
+    encs, writers, counts = [None] * k, [None] * k, [0] * k
+    try:
+        for chs in chunk_tuples:
+            if len(chs) != k:
+                raise ValueError(f"write_videos: {len(chs)} chunks for {k} videos")
+            for j, ch in enumerate(chs):
+                if not isinstance(ch, torch.Tensor):
+                    ch = torch.as_tensor(np.ascontiguousarray(ch))
+                if ch.dim() == 3:
+                    ch = ch[None]
+                if not ch.is_cuda:
+                    ch = ch.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+                if encs[j] is None:
+                    encs[j] = JpegEncoder(int(ch.shape[1]), int(ch.shape[2]), quality=quality, subsampling=subsampling, device=ch.device)
+                jpgs = encs[j].encode(ch)
+                if writers[j] is None:
+                    writers[j] = AviMjpegWriter(paths[j], encs[j].W, encs[j].H, fps=fps)
+                for jpg in jpgs:
+                    writers[j].write(jpg)
+                    counts[j] += 1
+        if any(w is None for w in writers):
+            raise ValueError("write_videos: no frames")
+    finally:
+        for w in writers:
+            if w is not None:
+                w.close()
+    return list(zip(paths, counts))

@@ -6,8 +6,9 @@ behave/kinect_transform.py, behave/utils.py:41-70) with their signatures.  neura
 ``csrc/render.hip`` (``vt_render_rgb``; its rule is written down in that file's header): ``setup_renderer`` returns a parameter object in place of
 an ``nr.Renderer``.  The ground is rendered as a *static layer*: set up, binned and resolved once per camera, then the seed of every view's
 resolve (bit-identical to rendering the concatenated scene).  The video is ``video.write_video`` (Motion-JPEG AVI, GPU JPEG encoder; frames from
-``render_frames(..., on_device=True)`` never leave the device).  Not here: ``cv2.putText`` labels (no cv2), the ``-add_top`` pytorch3d view,
-``-w`` Procrustes alignment, PHOSA, contact spheres, lens distortion.
+``render_frames(..., on_device=True)`` never leave the device).  Contacts (``viz_contact``: one sphere per touching body part, or the touched object
+faces recoloured) come from ``csrc/contact.hip`` through ``ContactVisualizer``; the ``-add_top`` view is the same rasteriser behind a look-at
+transform, over the ``xy`` ground.  Not here: ``cv2.putText`` labels (no cv2), ``-w`` Procrustes alignment, PHOSA, lens distortion.
 """
 from __future__ import annotations
 
@@ -232,8 +233,8 @@ class ShadedRasterizer:
         self.last_entries = 0
 
     def render(self, verts, faces, colors, params: RenderParams, static: StaticLayer | None = None, K=None, want_depth=False, want_index=False):
-        """verts (B,NV,3) world-of-the-renderer coordinates (R, t of ``params`` are applied here), faces (NF,3), colors (NF,3) -> dict of
-        rgb (B,S,S,3), alpha (B,S,S), depth, face_index (device tensors)"""
+        """verts (B,NV,3) world-of-the-renderer coordinates (R, t of ``params`` are applied here), faces (NF,3), colors (NF,3) or one table per
+        view (B,NF,3) (vt_render_rgb_pv) -> dict of rgb (B,S,S,3), alpha (B,S,S), depth, face_index (device tensors)"""
         if not params.fill_back or params.near != NEAR or params.far != FAR:
             raise NotImplementedError("the rasteriser implements neural_renderer's defaults: fill_back, near 0.1, far 100")
         dev = self.device
@@ -243,8 +244,14 @@ class ShadedRasterizer:
         v = v.contiguous()
         B, NV = v.shape[0], v.shape[1]
         f = torch.as_tensor(faces, dtype=torch.int32, device=dev).reshape(-1, 3).contiguous()
-        c = torch.as_tensor(colors, dtype=torch.float32, device=dev).reshape(-1, 3).contiguous()
         NF = f.shape[0]
+        c = torch.as_tensor(colors, dtype=torch.float32, device=dev)
+        cpv = int(c.dim() == 3)
+        if cpv and c.shape[0] != B:
+            raise ValueError(f"per-view colours: {c.shape[0]} tables for {B} views")
+        c = c.reshape(-1, 3).contiguous()
+        if c.shape[0] != (B if cpv else 1) * NF:
+            raise ValueError(f"{c.shape[0]} face colours for {NF} faces")
         size, aa = int(params.image_size), int(bool(params.anti_aliasing))
         if static is not None and static.params_key != params.key():
             raise ValueError("static layer was built for another camera / size / light")
@@ -263,10 +270,13 @@ class ShadedRasterizer:
             nbytes = L.lib().vt_render_workspace_bytes(B, NF, size, aa, want)
             if self.ws is None or self.ws.numel() < nbytes:
                 self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            rc = L.lib().vt_render_rgb(L.dptr(v), B, NV, L.dptr(f), NF, L.dptr(c), L.dptr(Kd), kpv, float(params.orig_size),
-                                       light.ctypes.data_as(C.POINTER(C.c_float)), bg.ctypes.data_as(C.POINTER(C.c_float)),
-                                       static.h if static is not None else None, size, aa, L.dptr(rgb), L.dptr(alpha), L.dptr(depth), L.dptr(fidx),
-                                       L.dptr(self.ws), self.ws.numel(), C.byref(need), L.stream_ptr())
+            args = (L.dptr(Kd), kpv, float(params.orig_size), light.ctypes.data_as(C.POINTER(C.c_float)), bg.ctypes.data_as(C.POINTER(C.c_float)),
+                    static.h if static is not None else None, size, aa, L.dptr(rgb), L.dptr(alpha), L.dptr(depth), L.dptr(fidx),
+                    L.dptr(self.ws), self.ws.numel(), C.byref(need), L.stream_ptr())
+            if cpv:
+                rc = L.lib().vt_render_rgb_pv(L.dptr(v), B, NV, L.dptr(f), NF, L.dptr(c), 1, *args)
+            else:
+                rc = L.lib().vt_render_rgb(L.dptr(v), B, NV, L.dptr(f), NF, L.dptr(c), *args)
             if rc == 0 or need.value <= want:
                 break
             want = int(need.value * 1.25) + 1024                            # the list did not fit: grow to it and render again
@@ -284,10 +294,14 @@ def panels_u8(rgb, out, view_off, row0, nrows, col0, ncols, row_stride):
 
 
 class NrWrapper:
-    """nr_utils.py:663-808 (the camera-view path)"""
+    """nr_utils.py:663-808 (the camera-view path).  ``part_labels`` (6890,) body part of every SMPL vertex (paths.load_part_labels,
+    synthetic.part_labels): needed for ``viz_contact`` only."""
 
-    def __init__(self, device='cuda:0', image_size=1024, colors=None, contact_viz_type='sphere', dataset_name='behave', kid=1):
+    def __init__(self, device='cuda:0', image_size=1024, colors=None, contact_viz_type='sphere', dataset_name='behave', kid=1, part_labels=None):
+        if contact_viz_type not in ('sphere', 'face'):
+            raise ValueError(f"contact_viz_type must be 'sphere' or 'face', not {contact_viz_type!r}")
         self.device = device
+        self.contact_viz = None if part_labels is None else ContactVisualizer(part_labels, thres=0.04, radius=0.06, device=device)   # nr_utils.py:417
         self.colors = [list(c) for c in SMPL_OBJ_COLOR_LIST] if colors is None else colors
         self.smpl_color, self.obj_color = SMPL_OBJ_COLOR_LIST[0], SMPL_OBJ_COLOR_LIST[1]
         self.front_renderer = setup_renderer(image_size=image_size, dataset_name=dataset_name, kid=kid)
@@ -304,14 +318,34 @@ class NrWrapper:
             self._layers[key] = (checker, StaticLayer(cv[0], cf[0], ct.reshape(-1, 3), renderer, self.device))
         return self._layers[key][1]
 
+    def contacts(self):
+        if self.contact_viz is None:
+            raise ValueError("viz_contact=True needs the SMPL part labels: pass part_labels=(6890,) ints in [0, 14) (paths.load_part_labels(assets_root) "
+                             "or synthetic.part_labels(model)) to NrWrapper / RendererSide2side")
+        return self.contact_viz
+
     def prepare_render(self, meshes, viz_contact=False, colors=None, checker=None, radius=None):
-        """nr_utils.py:760-799 without contact spheres: verts (1,NV,3), faces (1,F,3), textures (1,F,1,1,1,3), ground appended last"""
-        if viz_contact:
-            raise NotImplementedError("contact spheres are not part of step 7")
+        """nr_utils.py:760-799: verts (1,NV,3), faces (1,F,3), textures (1,F,1,1,1,3), ground appended last.  ``viz_contact`` counts for exactly two
+        meshes [SMPL, object], like the reference: contact_viz_type 'sphere' appends one sphere per touching part, 'face' recolours the object."""
         render_color = self.colors if colors is None else colors
         verts_list = [torch.as_tensor(np.asarray(m.v), dtype=torch.float32).unsqueeze(0) for m in meshes]
         faces_list = [torch.as_tensor(np.asarray(m.f).astype(np.int32)) for m in meshes]
-        faces, textures = get_faces_and_textures(verts_list, faces_list, colors_list=list(render_color)[:len(meshes)])
+        color_list = [list(c) for c in list(render_color)[:len(meshes)]]
+        regions = self.contacts().get_contact_spheres(meshes[0], meshes[1], radius) if viz_contact and len(meshes) == 2 else {}
+        spheres = bool(regions) and self.contact_viz_type == 'sphere'
+        if spheres:
+            for part in sorted(regions):
+                color, sphere, _ = regions[part]
+                verts_list.append(torch.as_tensor(sphere.v, dtype=torch.float32).unsqueeze(0))
+                faces_list.append(torch.as_tensor(sphere.f.astype(np.int32)))
+                color_list.append(list(color))
+        faces, textures = get_faces_and_textures(verts_list, faces_list, colors_list=color_list)
+        if regions and not spheres:
+            cv = self.contact_viz
+            part = torch.full((1, verts_list[1].shape[1]), -1, dtype=torch.int32)
+            for p, (_, _, ind) in regions.items():
+                part[0, torch.as_tensor(ind)] = p
+            textures = cv.face_colors(part.to(cv.device), faces_list[1], faces_list[0].shape[0], textures.reshape(-1, 3)).cpu().reshape(1, -1, 1, 1, 1, 3)
         verts = torch.cat(verts_list, 1)
         if checker is not None:
             cv, cf, ct = checker.get_rends()
@@ -330,6 +364,137 @@ class NrWrapper:
         if ret_depth:
             return rend, mask, out["depth"][0].cpu().numpy()
         return rend, mask
+
+
+# ---- contacts: render/nr_utils.py:359-404 (ContactVisualizer), :100-122 (contact-coloured faces) --------------------------------------------------
+PARTS_NUM = 14
+# this project's own palette for the 14 body parts: hues 360 / 14 degrees apart at alternating value, so that neighbours in the list differ clearly
+PART_COLORS = np.array([[0.90, 0.10, 0.10], [0.55, 0.30, 0.05], [0.95, 0.75, 0.10], [0.45, 0.55, 0.05], [0.45, 0.90, 0.10], [0.05, 0.55, 0.15],
+                        [0.10, 0.90, 0.55], [0.05, 0.50, 0.50], [0.10, 0.70, 0.95], [0.05, 0.25, 0.60], [0.35, 0.25, 0.95], [0.40, 0.05, 0.60],
+                        [0.90, 0.15, 0.90], [0.60, 0.05, 0.30]], np.float64)
+
+
+def icosphere(subdivisions=2):
+    """Unit sphere template of the contact spheres: an icosahedron, every triangle split in four ``subdivisions`` times, vertices pushed to radius 1.
+    -> verts (10 * 4^s + 2, 3) float64, faces (20 * 4^s, 3) int32, outward winding.  PARITY UNPINNED: stands in for psbody's Sphere.to_mesh."""
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    verts = [np.asarray(x, np.float64) / np.linalg.norm(x) for x in v]
+    faces = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+             (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(subdivisions):
+        mid, out = {}, []
+
+        def m(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in mid:
+                x = verts[a] + verts[b]
+                verts.append(x / np.linalg.norm(x)); mid[key] = len(verts) - 1
+            return mid[key]
+        for a, b, c in faces:
+            ab, bc, ca = m(a, b), m(b, c), m(c, a)
+            out += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        faces = out
+    return np.stack(verts), np.asarray(faces, np.int32)
+
+
+def look_at_view_transform(eye, at, up):
+    """World -> view rotation R (3,3) and translation T (3,) in float64, applied as ``v @ R + T``: z = normalize(at - eye), x = normalize(cross(up, z)),
+    y = cross(z, x), R = [x y z] as columns, T = -(eye @ R).  PARITY UNPINNED: restated from pytorch3d's documented look_at_view_transform (not
+    installed); its fallback for an ``up`` parallel to the viewing direction is left out -- that case raises."""
+    eye, at, up = (np.asarray(a, np.float64).reshape(3) for a in (eye, at, up))
+    z = at - eye
+    if np.linalg.norm(z) < 1e-12:
+        raise ValueError("look_at_view_transform: eye and at coincide")
+    z = z / np.linalg.norm(z)
+    x = np.cross(up, z)
+    if np.linalg.norm(x) < 1e-5:
+        raise ValueError("look_at_view_transform: up is parallel to the viewing direction")
+    x = x / np.linalg.norm(x)
+    y = np.cross(z, x)
+    R = np.stack([x, y, z], 1)
+    return R, -(eye @ R)
+
+
+TOP_EYE, TOP_AT, TOP_UP = (0.0, -1.8, 2.5), (0.0, 0.0, 2.4), (0.0, -1.0, 0.0)        # render_side_comp.py:52-66 rend_topviews
+
+
+class ContactVisualizer:
+    """nr_utils.py:359-404 on the device (csrc/contact.hip).  ``part_labels`` (NVs,) ints in [0, P), P = len(part_colors) <= 32."""
+
+    def __init__(self, part_labels, thres=0.04, radius=0.08, part_colors=None, device='cuda:0'):
+        self.device = torch.device(device)
+        self.part_colors = np.array(PART_COLORS if part_colors is None else part_colors, np.float64).reshape(-1, 3)
+        self.P = len(self.part_colors)
+        lab = np.asarray(part_labels.cpu() if torch.is_tensor(part_labels) else part_labels).astype(np.int64).reshape(-1)
+        if not 0 < self.P <= 32 or lab.size == 0 or lab.min() < 0 or lab.max() >= self.P:
+            raise ValueError(f"part labels must lie in [0, {self.P}) (one colour per part, at most 32 parts)")
+        self.part_labels = lab.astype(np.int32)
+        self.thres, self.radius = float(thres), float(radius)
+        self.sphere_v, self.sphere_f = icosphere(2)
+        self.labels_d = torch.as_tensor(self.part_labels, device=self.device).contiguous()
+        self.unit_d = torch.as_tensor(self.sphere_v, dtype=torch.float32, device=self.device).contiguous()
+        self.palette_d = torch.as_tensor(self.part_colors, dtype=torch.float32, device=self.device).contiguous()
+
+    def _verts(self, v):
+        v = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).to(self.device, torch.float32)
+        return (v[None] if v.dim() == 2 else v).contiguous()
+
+    def regions(self, smpl_verts, obj_verts):
+        """vt_contact_regions: smpl_verts (B,NVs,3), obj_verts (B,NVo,3) -> device tensors nn_idx (B,NVo) int32, nn_dist (B,NVo), part (B,NVo) int32
+        (-1 = no contact), count (B,P) int32, centre (B,P,3)"""
+        sv, ov = self._verts(smpl_verts), self._verts(obj_verts)
+        if sv.shape[0] != ov.shape[0] or sv.shape[1] != len(self.part_labels) or sv.shape[2] != 3 or ov.shape[2] != 3:
+            raise ValueError(f"regions: smpl_verts {tuple(sv.shape)} / obj_verts {tuple(ov.shape)} do not match {len(self.part_labels)} part labels")
+        B, NVs, NVo, dev = sv.shape[0], sv.shape[1], ov.shape[1], self.device
+        out = {"nn_idx": torch.empty(B, NVo, dtype=torch.int32, device=dev), "nn_dist": torch.empty(B, NVo, device=dev),
+               "part": torch.empty(B, NVo, dtype=torch.int32, device=dev), "count": torch.empty(B, self.P, dtype=torch.int32, device=dev),
+               "centre": torch.empty(B, self.P, 3, device=dev)}
+        with torch.cuda.device(dev):
+            L.check(L.lib().vt_contact_regions(L.dptr(sv), L.dptr(self.labels_d), L.dptr(ov), B, NVs, NVo, self.P, self.thres, L.dptr(out["nn_idx"]),
+                                               L.dptr(out["nn_dist"]), L.dptr(out["part"]), L.dptr(out["count"]), L.dptr(out["centre"]), L.stream_ptr()))
+        return out
+
+    def spheres(self, regions, radius=None):
+        """vt_contact_spheres -> (B, P * 162, 3): sphere p of every frame, collapsed to one point where part p does not touch"""
+        centre, count = regions["centre"], regions["count"]
+        B, NSV = centre.shape[0], self.unit_d.shape[0]
+        out = torch.empty(B, self.P * NSV, 3, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().vt_contact_spheres(L.dptr(centre), L.dptr(count), B, self.P, L.dptr(self.unit_d), NSV,
+                                               float(self.radius if radius is None else radius), L.dptr(out), L.stream_ptr()))
+        return out
+
+    def sphere_faces_colors(self, vert_offset):
+        """faces (P * 320, 3) int32 of the P spheres appended at ``vert_offset``, and their colours (P * 320, 3) float32"""
+        NSV, NSF = len(self.sphere_v), len(self.sphere_f)
+        f = np.concatenate([self.sphere_f + vert_offset + p * NSV for p in range(self.P)]).astype(np.int32)
+        return f, np.repeat(self.part_colors.astype(np.float32), NSF, 0)
+
+    def face_colors(self, part, obj_faces, face_off, base_colors):
+        """vt_contact_face_colors: part (B,NVo) -> (B,NF,3) colour tables, the object's faces (rows face_off.. of ``base_colors``) in contact recoloured"""
+        part = part.contiguous()
+        B, NVo = part.shape
+        f = torch.as_tensor(np.asarray(obj_faces.cpu() if torch.is_tensor(obj_faces) else obj_faces).astype(np.int32), device=self.device).reshape(-1, 3).contiguous()
+        if f.numel() == 0 or int(f.min()) < 0 or int(f.max()) >= NVo:
+            raise ValueError("face_colors: object faces index outside the object's vertices")
+        base = torch.as_tensor(base_colors, dtype=torch.float32, device=self.device).reshape(-1, 3).contiguous()
+        out = torch.empty(B, base.shape[0], 3, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().vt_contact_face_colors(L.dptr(part), B, NVo, L.dptr(f), f.shape[0], int(face_off), L.dptr(base), base.shape[0],
+                                                   L.dptr(self.palette_d), self.P, L.dptr(out), L.stream_ptr()))
+        return out
+
+    def get_contact_spheres(self, smpl: Mesh, obj: Mesh, radius=None):
+        """nr_utils.py:380-404 for one mesh pair: {part: (colour, sphere Mesh, indices of the object's contact vertices of that part)}, {} without contact"""
+        reg = self.regions(np.asarray(smpl.v), np.asarray(obj.v))
+        count = reg["count"][0].cpu().numpy()
+        if count.sum() == 0:
+            return {}
+        part = reg["part"][0].cpu().numpy()
+        sph = self.spheres(reg, radius).reshape(self.P, -1, 3).cpu().numpy()
+        return {int(p): (self.part_colors[p], Mesh(v=sph[p].astype(np.float64), f=self.sphere_f.copy()), np.nonzero(part == p)[0])
+                for p in np.nonzero(count)[0]}
 
 
 # ---- behave/utils.py:41-70, behave/kinect_transform.py -------------------------------------------------------------------------------------------
@@ -416,12 +581,17 @@ def object_verts(temp_v, obj_angles, obj_trans, obj_scales):
 class RendererSide2side:
     """Side-by-side frames: [input rgb | camera kid recon_1 .. recon_n | camera kid + 1 recon_1 .. recon_n], each panel the rows [:0.75 size] and
     columns [0.2 size, 0.8 size) of a size x size render (render_side_comp.py:71-98, render_recon.py:41-160).  Camera 1's intrinsics render every
-    view (the reference's single front renderer, NrWrapper(kid=1))."""
+    view (the reference's single front renderer, NrWrapper(kid=1)).  ``part_labels`` / ``contact_viz_type``: see NrWrapper (for ``viz_contact``)."""
 
-    def __init__(self, image_size=1200, gender='male', dataset_name='behave', kid=None, device='cuda:0', xcut_start=0.2, xcut_end=0.8):
+    def __init__(self, image_size=1200, gender='male', dataset_name='behave', kid=None, device='cuda:0', xcut_start=0.2, xcut_end=0.8,
+                 part_labels=None, contact_viz_type='sphere'):
         self.test_id = (1 if dataset_name == 'behave' else 0) if kid is None else kid
         self.aspect_ratio = 0.75 if dataset_name == 'behave' else 9 / 16.
-        self.nrwrapper = NrWrapper(image_size=image_size, colors=COLOR_LIST3, dataset_name=dataset_name, device=device)
+        self.nrwrapper = NrWrapper(image_size=image_size, colors=COLOR_LIST3, dataset_name=dataset_name, device=device, part_labels=part_labels,
+                                   contact_viz_type=contact_viz_type)
+        self._ground_xy = None
+        R, T = look_at_view_transform(TOP_EYE, TOP_AT, TOP_UP)
+        self.top_R, self.top_T = R.astype(np.float32), T.astype(np.float32)
         checker_xz = CheckerBoard()
         psize = 80.0
         checker_xz.init_checker(np.array([-psize / 2., 1.5, -psize / 2.]), 'xz', square_size=0.5, xlength=psize, ylength=psize)
@@ -436,12 +606,41 @@ class RendererSide2side:
         cs, ce = self.get_xcuts(self.image_size)
         return int(self.aspect_ratio * self.image_size), (ce - cs) * (1 + 2 * n_recons), 3
 
-    def render_frames(self, recons, temp_v, temp_f, smpl_handle, kin, rgb=None, start=0, end=None, interval=1, chunk=8, on_device=False):
+    @property
+    def ground_xy(self):
+        """render_recon.py:59-62: the xy board of the top view, built on first use"""
+        if self._ground_xy is None:
+            ck = CheckerBoard()
+            ck.init_checker(np.array([-40., -40., 4.0]), 'xy', square_size=0.75, xlength=80, ylength=80)
+            self._ground_xy = ck
+        return self._ground_xy
+
+    def top_shape(self, n_recons):
+        """shape of a top-view strip [rgb panel | top view of recon_1 .. recon_n] after the cut of its top 0.3 (render_recon.py:172-178)"""
+        H, _, _ = self.frame_shape(n_recons)
+        cs, ce = self.get_xcuts(self.image_size)
+        return H - int(0.3 * H), (ce - cs) * (1 + n_recons), 3
+
+    def top_transform(self, verts):
+        """packed coordinates -> the top view's camera (render_side_comp.py:52-66): v @ R + T of look_at_view_transform(TOP_EYE, TOP_AT, TOP_UP), in
+        fp32, term by term (x R[0] + y R[1]) + z R[2] + T so that the result does not depend on the batch shape"""
+        R = torch.as_tensor(self.top_R, device=verts.device); T = torch.as_tensor(self.top_T, device=verts.device)
+        return (verts[..., 0:1] * R[0] + verts[..., 1:2] * R[1]) + verts[..., 2:3] * R[2] + T
+
+    def render_frames(self, recons, temp_v, temp_f, smpl_handle, kin, rgb=None, start=0, end=None, interval=1, chunk=8, on_device=False,
+                      viz_contact=False, add_top=False):
         """Generator of uint8 frame chunks (n, H, W, 3) for frames start:end:interval of the packed ``recons`` (dicts with poses (T,156), betas,
         trans, obj_angles (T,3,3), obj_trans, obj_scales).  ``smpl_handle``: ops.SmplhHandle of the sequence's SMPL-H model; ``kin``: KinectTransform;
         ``rgb``: None (black panel), a sequence or a callable frame index -> (h,w,3) uint8 image of camera test_id.  Every chunk renders
         chunk x 2 x len(recons) views in one vt_render_rgb call, the ground as one static layer.  ``on_device=True`` yields the chunks as uint8 device
-        tensors (for ``video.write_video``) instead of host arrays."""
+        tensors (for ``video.write_video``) instead of host arrays.
+
+        ``viz_contact``: the contact search (ContactVisualizer.regions) runs once per (frame, recon) in packed coordinates; with contact_viz_type
+        'sphere' the 14 spheres of every recon join its vertex block before the camera transforms (parts that do not touch collapse to a point:
+        zero-area faces, culled by the rasteriser's set-up), with 'face' every view gets its own face-colour table.  ``add_top``: the generator
+        yields (frames, top_frames) pairs, top_frames (n,) + top_shape(len(recons)): [rgb panel | top-down view of every recon] over the xy ground
+        (render_side_comp.py:52-66, render_recon.py:172-178).  Every frame is written: the reference loses the first top-view frame while it opens
+        its second writer, which is not copied."""
         dev = torch.device(self.device)
         size = self.image_size
         cs, ce = self.get_xcuts(size)
@@ -459,26 +658,47 @@ class RendererSide2side:
         faces = np.concatenate([smpl_f, temp_f + nvs], 0).astype(np.int32)
         colors = np.concatenate([np.tile(np.asarray(self.nrwrapper.colors[0], np.float32), (len(smpl_f), 1)),
                                  np.tile(np.asarray(self.nrwrapper.colors[1], np.float32), (len(temp_f), 1))], 0)
-        faces_d = torch.as_tensor(faces, device=dev); colors_d = torch.as_tensor(colors, device=dev)
         tv = torch.as_tensor(np.asarray(temp_v), dtype=torch.float32, device=dev)
+        nv_mesh = nvs + tv.shape[0]
+        cviz = self.nrwrapper.contacts() if viz_contact else None
+        spheres = viz_contact and self.nrwrapper.contact_viz_type == 'sphere'
+        if spheres:
+            sf, sc = cviz.sphere_faces_colors(nv_mesh)
+            faces, colors = np.concatenate([faces, sf], 0), np.concatenate([colors, sc], 0)
+        faces_d = torch.as_tensor(faces, device=dev); colors_d = torch.as_tensor(colors, device=dev)
+        if add_top:
+            top_layer = self.nrwrapper.static_layer(renderer, self.ground_xy)
+            Ht, Wt, _ = self.top_shape(n)
+            cut = H - Ht
         kids = [self.test_id, self.test_id + 1]
         with torch.cuda.device(dev):
             for c0 in range(0, len(frames), chunk):
                 idx = frames[c0:c0 + chunk]
                 nc = len(idx)
                 ii = torch.as_tensor(idx, device=dev)
-                per_recon = []
+                per_recon, per_colors = [], []
                 for d in recons:
                     g = lambda k, w: torch.as_tensor(np.asarray(d[k], np.float32).reshape(T, w), device=dev)[ii].contiguous()
                     sv, _, _ = ops.smplh_forward(smpl_handle, g("poses", 156), g("betas", 10), g("trans", 3))
                     R = g("obj_angles", 9).reshape(nc, 3, 3); t = g("obj_trans", 3); s = g("obj_scales", 1)
                     ov = (tv[None] @ R + t[:, None]) * s[:, :, None]
-                    per_recon.append(torch.cat([sv.detach(), ov], 1))
+                    block = [sv.detach(), ov]
+                    if viz_contact:
+                        reg = cviz.regions(block[0], ov)
+                        if spheres:
+                            block.append(cviz.spheres(reg))
+                        else:
+                            per_colors.append(cviz.face_colors(reg["part"], temp_f, len(smpl_f), colors_d))
+                    per_recon.append(torch.cat(block, 1))
                 views = torch.stack([torch.stack([kin.world2local_torch(v, k) for v in per_recon], 1) for k in kids], 1)   # (nc, 2, n, NV, 3)
                 views = views.reshape(nc * 2 * n, views.shape[-2], 3).contiguous()
-                if bool((views[..., 2].amin() < 0).item()):
+                if bool((views[:, :nv_mesh, 2].amin() < 0).item()):
                     raise ValueError("a mesh lies behind the camera (render_side_comp.py:86-90 allows that for PHOSA only)")
-                out = self.nrwrapper.raster.render(views, faces_d, colors_d, renderer, static=layer)
+                cols = colors_d
+                if per_colors:                                                      # (nc, n, NF, 3): the same table for both cameras of a frame
+                    pc = torch.stack(per_colors, 1)
+                    cols = pc[:, None].expand(nc, 2, n, *pc.shape[2:]).reshape(nc * 2 * n, -1, 3)
+                out = self.nrwrapper.raster.render(views, faces_d, cols, renderer, static=layer)
                 buf = torch.zeros(nc, H, W, 3, dtype=torch.uint8, device=dev)
                 b = torch.arange(nc * 2 * n, device=dev)
                 off = (b // (2 * n)) * (H * W * 3) + (1 + b % (2 * n)) * (pw * 3)
@@ -488,7 +708,17 @@ class RendererSide2side:
                         img = rgb(i) if callable(rgb) else rgb[i]
                         img = resize_bilinear_hw(np.asarray(img), H, size)[:, cs:ce]
                         buf[j, :, :pw] = torch.as_tensor(np.ascontiguousarray(img), device=dev)
-                yield buf if on_device else buf.cpu().numpy()
+                if not add_top:
+                    yield buf if on_device else buf.cpu().numpy()
+                    continue
+                tviews = self.top_transform(torch.stack(per_recon, 1)).reshape(nc * n, -1, 3).contiguous()
+                tcols = torch.stack(per_colors, 1).reshape(nc * n, -1, 3) if per_colors else colors_d
+                tout = self.nrwrapper.raster.render(tviews, faces_d, tcols, renderer, static=top_layer)
+                tbuf = torch.zeros(nc, Ht, Wt, 3, dtype=torch.uint8, device=dev)
+                b = torch.arange(nc * n, device=dev)
+                panels_u8(tout["rgb"], tbuf, (b // n) * (Ht * Wt * 3) + (1 + b % n) * (pw * 3), cut, Ht, cs, pw, Wt * 3)
+                tbuf[:, :, :pw] = buf[:, cut:, :pw]
+                yield (buf, tbuf) if on_device else (buf.cpu().numpy(), tbuf.cpu().numpy())
 
 
 def write_frames(frames, outdir, start=0, prefix="frame"):
