@@ -587,6 +587,25 @@ long vt_jpeg_workspace_bytes(int n, int H, int W, int subsampling, long long *ma
 int vt_jpeg_encode(const unsigned char *rgb, int n, int H, int W, long long frame_stride, long long row_stride, int quality, int subsampling, void *ws,
                    long ws_bytes, unsigned char *out, long long out_cap, long long *offsets, void *stream);
 
+/* ---- SIF-Net input crops from decoded frames (data/train_data.py:143-162 prepare_image_crop; vistracker_amd/sequence_io.py prepare_crops) -------------------
+ * uint8 frames in device memory in, channels 0..4 of the (B,8,S,S) fp32 network tensor out; the arithmetic contract is written in inputs.hip's header and
+ * restated with integers in tests/inputs_model.py.  Both calls reproduce the host path (sequence_io.masks2bbox, crop, resize_bilinear, the compose of
+ * SequenceLoader.load_crop) bit for bit; integer atomics only, results independent of scheduling, of B and of a frame's place in the batch.
+ *
+ * vt_mask_bbox (data/base_data.py:139-157 masks2bbox): pm, om (B,H,W) uint8; a pixel counts when (uint8)(pm + om) > thres, the sum wrapping in uint8 as the
+ *   reference's accumulator does.  box (B,4) int32 = xmin, ymin, xmax, ymax, inclusive; (W, H, -1, -1) for a frame without such a pixel (the caller maps it
+ *   to EMPTY_BBOX).  H * W <= 2^30, B <= 65535.
+ * vt_crop_resize_compose (data/train_data.py:143-162, data/base_data.py:204-233 crop, :252-265 compose_images): rgb (B,H,W,3), pm, om (B,H,W) uint8;
+ *   corners (B,4) int32 on the device = tl.x, tl.y, br.x, br.y of each frame's crop, rounded on the host as crop() rounds them (each extent br - tl is
+ *   crop_size, or crop_size +- 1 for an odd crop_size: numpy rounds halves to even); a frame whose extents are not within 1 of crop_size, or with a corner beyond
+ *   +-2^29, is written as zeros and reads nothing (crop_size < 2^28).  Only image pixels x in [max(0, tl.x), min(W - 1, br.x)) (likewise y) are read, the rest of the crop is 0.  Bilinear resize of the crop to
+ *   out_size x out_size with half-pixel centres in fp32, q = clip(floor(x + 0.5), 0, 255), value = table[q] with table = 256 device floats
+ *   float32(q / 255.0); rgb channels are zeroed where neither resized mask reaches 128.  Frame b is written at out + b * frame_stride floats
+ *   (frame_stride >= 5 out_size^2; 8 out_size^2 for the network tensor), channels 0..4 only. */
+int vt_mask_bbox(const unsigned char *pm, const unsigned char *om, int B, int H, int W, int thres, int *box, void *stream);
+int vt_crop_resize_compose(const unsigned char *rgb, const unsigned char *pm, const unsigned char *om, int B, int H, int W, const int *corners, int crop_size,
+                           int out_size, const float *table, float *out, long long frame_stride, void *stream);
+
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two
  * workgroups of 256 threads per CU, non-trivial operands), out[1] = shader clock sustained during it (MHz: s_memtime against the 100 MHz s_memrealtime),

@@ -140,6 +140,8 @@ SIGNATURES = {
     "vt_jpeg_workspace_bytes": (cl, [ci, ci, ci, ci, C.POINTER(C.c_longlong)]),
     "vt_jpeg_encode": (ci, [fp, ci, ci, ci, C.c_longlong, C.c_longlong, ci, ci, vp, cl, vp, C.c_longlong,
                             C.POINTER(C.c_longlong), vp]),
+    "vt_mask_bbox": (ci, [fp, fp, ci, ci, ci, ci, fp, vp]),
+    "vt_crop_resize_compose": (ci, [fp, fp, fp, ci, ci, ci, fp, ci, ci, fp, fp, C.c_longlong, vp]),
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
 }

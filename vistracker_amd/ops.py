@@ -505,6 +505,60 @@ def silhouette(verts, faces, K, size=256, eps=1e-4):
 
 
 # --------------------------------------------------------------------------------------------------
+# network inputs from decoded frames (csrc/inputs.hip)
+# --------------------------------------------------------------------------------------------------
+def div255_table():
+    """host (256,) float32: float32(q / 255.0), the value the host loader stores for grey level q (uint8 / 255.0 in float64, narrowed by astype)"""
+    return (np.arange(256, dtype=np.float64) / 255.0).astype(np.float32)
+
+
+_DIV255 = {}          # device index -> the table on that device
+
+
+def _u8(t, name):
+    if t.dtype != torch.uint8:
+        raise L.VtError(f"{name}: uint8 expected, got {t.dtype}")
+    return t
+
+
+def mask_bbox(pm, om, thres=127):
+    """vt_mask_bbox: pm, om (B,H,W) uint8 device tensors -> (B,4) int32 device tensor xmin, ymin, xmax, ymax (inclusive) of the pixels with
+    (uint8)(pm + om) > thres; (W, H, -1, -1) for a frame without one.  ``sequence_io.masks2bbox`` for a batch."""
+    B, H, W = pm.shape
+    if tuple(om.shape) != (B, H, W):
+        raise L.VtError(f"mask_bbox: masks of {tuple(pm.shape)} and {tuple(om.shape)}")
+    p, o = L.dptr(_u8(pm, "pm")), L.dptr(_u8(om, "om"))
+    box = torch.empty(B, 4, dtype=torch.int32, device=pm.device)
+    L.check(L.lib().vt_mask_bbox(p, o, B, H, W, int(thres), L.dptr(box), L.stream_ptr()))
+    return box
+
+
+def crop_resize_compose(rgb, pm, om, corners, crop_size, out_size, out=None):
+    """vt_crop_resize_compose: rgb (B,H,W,3), pm, om (B,H,W) uint8 device tensors; ``corners`` (B,4) host integers tl.x, tl.y, br.x, br.y of each frame's
+    crop as ``sequence_io.crop`` rounds them.  Writes channels 0..4 of ``out`` (B,C>=5,S,S) float32 (allocated as (B,5,S,S) when None) = RGB * (person |
+    object), person mask, object mask at the network size, bit for bit what ``SequenceLoader.load_crop`` computes on the host; other channels are untouched."""
+    B, H, W = pm.shape
+    S, cs = int(out_size), int(crop_size)
+    if tuple(rgb.shape) != (B, H, W, 3) or tuple(om.shape) != (B, H, W):
+        raise L.VtError(f"crop_resize_compose: rgb {tuple(rgb.shape)}, masks {tuple(pm.shape)} and {tuple(om.shape)}")
+    ptrs = [L.dptr(_u8(t, n)) for t, n in ((rgb, "rgb"), (pm, "pm"), (om, "om"))]
+    c = np.ascontiguousarray(corners, dtype=np.int64).reshape(-1, 4)
+    ext = np.stack([c[:, 2] - c[:, 0], c[:, 3] - c[:, 1]], 1)
+    if c.shape[0] != B or (ext <= 0).any() or (np.abs(ext - cs) > 1).any() or np.abs(c).max(initial=0) >= 2 ** 29:
+        raise ValueError(f"crop_resize_compose: corners {c.tolist()} are not {B} crops of size {cs}")
+    if out is None:
+        out = torch.empty(B, 5, S, S, device=rgb.device)
+    elif out.dtype != torch.float32 or out.dim() != 4 or out.shape[0] != B or out.shape[1] < 5 or tuple(out.shape[2:]) != (S, S):
+        raise L.VtError(f"crop_resize_compose: out {tuple(out.shape)} {out.dtype} for {B} crops of {S} x {S}")
+    dev = rgb.device.index
+    if dev not in _DIV255:
+        _DIV255[dev] = torch.as_tensor(div255_table(), device=rgb.device)
+    cd = torch.as_tensor(c.astype(np.int32), device=rgb.device)
+    L.check(L.lib().vt_crop_resize_compose(*ptrs, B, H, W, L.dptr(cd), cs, S, L.dptr(_DIV255[dev]), L.dptr(out), out.stride(0), L.stream_ptr()))
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
 # Adam
 # --------------------------------------------------------------------------------------------------
 class FusedAdam:

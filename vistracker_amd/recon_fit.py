@@ -63,6 +63,9 @@ class ReconFitterBase:
 
 
 class ReconFitterTriVisFull(ReconFitterBase):
+    # what ``sequence_loader`` uses; ``from_paths`` sets both on the instance
+    smpl_faces, loader_options = None, {"device_prep": False, "decode_workers": 0}
+
     def __init__(self, seq_folder=None, debug=False, outpath=None, args=None, *, smpl_model, regressors, priors, decoders,
                  part_labels, scan, obj_points, device="cuda:0"):
         """``seq_folder / debug / outpath / args`` are accepted for signature compatibility (recon_fit_trivis_full.py:477-485) and
@@ -82,13 +85,15 @@ class ReconFitterTriVisFull(ReconFitterBase):
         self.profile = False    # True: fit_recon_batch records synchronised wall-clock per part in self.last["seconds"]
 
     @classmethod
-    def from_paths(cls, seq_folder, debug=False, outpath=None, args=None, *, paths="PATHS.yml", obj_name=None, device="cuda:0"):
+    def from_paths(cls, seq_folder, debug=False, outpath=None, args=None, *, paths="PATHS.yml", obj_name=None, device="cuda:0", device_prep=False,
+                   decode_workers=0):
         """The reference's constructor call, unchanged: ``ReconFitterTriVisFull.from_paths(seq_folder, debug, outpath, args)``
         (recon_fit_trivis_full.py:477-485).  Reads what ``ReconFitterBase.__init__`` reads (recon_fit_base.py:53-120) from the places PATHS.yml names:
         SMPL-H model of the sequence's gender, landmark regressors + priors, part labels, the object template of <seq_folder>/info.json
         (centred, PCA axes, 3000 surface samples) and the SIF-Net checkpoint of ``args.exp_name`` (``args.checkpoint`` or best / latest) --
         ``vistracker_amd.paths``.  Also sets what the reference keeps on the instance: ``gender``, ``pca_init``, ``obj_points``, ``obj_scale``,
-        ``part_labels``, ``net_in_size``, ``z_0``, ``state_dict`` (for ``SIFNetQuery.from_state_dict``)."""
+        ``part_labels``, ``net_in_size``, ``z_0``, ``state_dict`` (for ``SIFNetQuery.from_state_dict``).  ``device_prep`` / ``decode_workers`` are the
+        options ``sequence_loader`` hands to ``SequenceLoader`` (both off: the host loader, one frame after another)."""
         from . import paths as P
         kw, meta = P.recon_inputs(seq_folder, args, paths, obj_name)
         self = cls(seq_folder, debug, outpath if outpath is not None else meta["outpath"], args, device=device, **kw)
@@ -99,7 +104,19 @@ class ReconFitterTriVisFull(ReconFitterBase):
         self.part_labels = torch.as_tensor(kw["part_labels"], device=device)
         self.net_in_size = args.net_img_size[0] if args is not None and hasattr(args, "net_img_size") else 512
         self.z_0 = getattr(args, "z_0", 2.2)
+        self.smpl_faces = kw["smpl_model"]["f"]
+        self.loader_options = {"device_prep": bool(device_prep), "decode_workers": int(decode_workers)}
         return self
+
+    def sequence_loader(self, image_files, batch_size, smplt, faces=None, image_size=None, crop_size=1200):
+        """the ``loader=`` of ``fit_recon`` for ``k1.color.jpg`` files of a sequence folder (``TestDataTriplane(...).get_loader(shuffle=False)``,
+        data/testdata_triplane.py:42-74): a ``sequence_io.SequenceLoader`` on this fitter's context with the loader options given to ``from_paths``.
+        ``smplt``: packed SMPL-T parameters of the frames; ``faces``: SMPL faces when the fitter was not built by ``from_paths``."""
+        from .sequence_io import SequenceLoader
+        faces = faces if faces is not None else self.smpl_faces
+        assert faces is not None, "sequence_loader needs faces= on a fitter that from_paths did not build"
+        size = image_size if image_size is not None else getattr(self, "net_in_size", 512)
+        return SequenceLoader(image_files, batch_size, smplt, self.ctx, faces, image_size=size, crop_size=crop_size, device=self.device, **self.loader_options)
 
     # ---- schedules / weights (Appendix A.2 of SURVEY.md) ---------------------------------------------------
     def get_loss_weights(self):

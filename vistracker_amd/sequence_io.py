@@ -110,17 +110,152 @@ def resize_bilinear_hw(img: np.ndarray, height: int, width: int) -> np.ndarray:
     return out
 
 
+# ---- decoding and the device path of prepare_image_crop ------------------------------------------------------------------------------
+MAX_DECODE_WORKERS = 16
+
+
+def decode_frame(rgb_file):
+    """the three images of a frame as PIL decodes them: rgb (H,W,3), person mask, object mask (masks as stored: (H,W) or (H,W,C))"""
+    base = rgb_file[:-len(".color.jpg")]
+    pm = _load_image(_first_existing(base, [".person_mask.png", ".person_mask.jpg"]))
+    om = _load_image(_first_existing(base, [".obj_rend_mask.png", ".obj_rend_mask.jpg", ".obj_mask.png", ".obj_mask.jpg"]))
+    return _load_image(rgb_file), pm, om
+
+
+def decode_threads(decode_workers):
+    """threads a ``decode_workers`` setting gives: min(decode_workers, 16), 0 for no pool; never sized by the machine's CPU count"""
+    return max(0, min(int(decode_workers), MAX_DECODE_WORKERS))
+
+
+def _decode_pool(decode_workers):
+    """ThreadPoolExecutor of ``decode_threads`` threads (PIL releases the GIL while it decodes), or None for decode_workers <= 0"""
+    n = decode_threads(decode_workers)
+    if n <= 0:
+        return None
+    from concurrent.futures import ThreadPoolExecutor
+    return ThreadPoolExecutor(max_workers=n, thread_name_prefix="vt-decode")
+
+
+def check_crop_center(center, iw, rgb_file):
+    assert (center > 0).all() and center[0] < iw and center[1] < iw, f"invalid crop center value {center} for image {rgb_file}"
+
+
+def bbox_from_device(box):
+    """a row of ``ops.mask_bbox`` (xmin, ymin, xmax, ymax inclusive; xmax < 0: no pixel) -> what ``masks2bbox`` returns for the frame"""
+    x0, y0, x1, y1 = (int(v) for v in box)
+    if x1 < 0:
+        return np.array(EMPTY_BBOX[:2]), np.array(EMPTY_BBOX[2:])
+    return np.array([x0, y0]), np.array([x1 + 1, y1 + 1])
+
+
+def device_crops(decoded, files, out, crop_size, image_size):
+    """prepare_image_crop (data/train_data.py:143-162) of decoded frames on the device: ``decoded`` = ``decode_frame`` results, ``out`` (n,C>=5,S,S)
+    float32 device tensor whose channels 0..4 are written (csrc/inputs.hip: the same values as ``SequenceLoader.load_crop``, bit for bit).  Frames of
+    equal size go through one pinned staging buffer, one upload, ``vt_mask_bbox``, one read-back of the boxes, the host's integer rounding of centre
+    and corners and ``vt_crop_resize_compose``.  Returns the crop centres (n,2) float32 (host)."""
+    from . import ops
+    n = len(decoded)
+    centers = np.zeros((n, 2), np.float32)
+    groups = {}
+    for i, (rgb, pm, om) in enumerate(decoded):
+        if rgb.ndim != 3 or rgb.shape[2] != 3 or pm.shape[:2] != rgb.shape[:2] or om.shape[:2] != rgb.shape[:2]:
+            raise ValueError(f"{files[i]}: rgb {rgb.shape}, masks {pm.shape} and {om.shape}")
+        if rgb.dtype != np.uint8 or pm.dtype != np.uint8 or om.dtype != np.uint8:          # e.g. a 16-bit or 1-bit PNG: the staging buffer would wrap or cast it
+            raise ValueError(f"{files[i]}: the device path takes 8-bit images, got rgb {rgb.dtype}, masks {pm.dtype} and {om.dtype}")
+        groups.setdefault(rgb.shape[:2], []).append(i)
+    with torch.cuda.device(out.device):
+        for (H, W), idx in groups.items():
+            g, hw = len(idx), H * W
+            stage = torch.empty(5 * g * hw, dtype=torch.uint8, pin_memory=True)          # masks first: their rows stay 16-byte aligned
+            host = stage.numpy()
+            h_pm, h_om, h_rgb = host[:g * hw].reshape(g, H, W), host[g * hw:2 * g * hw].reshape(g, H, W), host[2 * g * hw:].reshape(g, H, W, 3)
+            for k, i in enumerate(idx):
+                rgb, pm, om = decoded[i]
+                h_rgb[k] = rgb; h_pm[k] = pm if pm.ndim == 2 else pm[..., 0]; h_om[k] = om if om.ndim == 2 else om[..., 0]
+            dev = stage.to(out.device, non_blocking=True)
+            d_pm, d_om, d_rgb = dev[:g * hw].view(g, H, W), dev[g * hw:2 * g * hw].view(g, H, W), dev[2 * g * hw:].view(g, H, W, 3)
+            boxes = ops.mask_bbox(d_pm, d_om, 127).cpu().numpy()                          # the one synchronisation of the group
+            corners = np.zeros((g, 4), np.int64)
+            for k, i in enumerate(idx):
+                bmin, bmax = bbox_from_device(boxes[k])
+                center = (bmin + bmax) // 2
+                check_crop_center(center, W, files[i])
+                corners[k, :2] = np.round(center - crop_size / 2).astype(int); corners[k, 2:] = np.round(center + crop_size / 2).astype(int)      # crop()
+                centers[i] = center.astype(np.float32)
+            if idx == list(range(idx[0], idx[0] + g)):
+                ops.crop_resize_compose(d_rgb, d_pm, d_om, corners, crop_size, image_size, out=out[idx[0]:idx[0] + g])
+            else:                                                                         # frames of this size are scattered over the chunk
+                out[idx, :5] = ops.crop_resize_compose(d_rgb, d_pm, d_om, corners, crop_size, image_size)
+    return centers
+
+
+def prepare_crops(image_files, image_size=512, crop_size=1200, device="cuda:0", device_prep=True, decode_workers=0, chunk=16):
+    """network inputs of a list of ``k1.color.jpg`` files: ``images5`` (n,5,S,S) float32 on ``device`` (RGB * (person | object), person mask, object
+    mask) and the crop centres (n,2) float32 on the host -- ``seq["images5"]`` and ``seq["crop_center"]`` of ``SequencePipeline.run``.  ``device_prep``:
+    crop / resize / compose with the HIP kernels (``device_crops``), else with the host path of ``SequenceLoader.load_crop``; the values are the same.
+    ``decode_workers`` > 0 decodes in that many threads (at most 16), one chunk of ``chunk`` frames ahead."""
+    files = list(image_files)
+    S = int(image_size)
+    images5 = torch.empty(len(files), 5, S, S, device=device)
+    centers = np.zeros((len(files), 2), np.float32)
+    for s, part, decoded in _decoded_chunks(files, int(chunk), decode_workers):
+        if device_prep:
+            centers[s:s + len(part)] = device_crops(decoded, part, images5[s:s + len(part)], int(crop_size), S)
+        else:
+            crops = [host_crop(d, f, int(crop_size), S) for d, f in zip(decoded, part)]
+            images5[s:s + len(part)] = torch.as_tensor(np.stack([c[0] for c in crops]), device=device)
+            centers[s:s + len(part)] = np.stack([c[1] for c in crops])
+    return images5, centers
+
+
+def _decoded_chunks(files, chunk, decode_workers):
+    """(start, files of the chunk, their decoded frames) in order; with a pool, chunk k + 1 is being decoded while chunk k is consumed"""
+    pool = _decode_pool(decode_workers)
+    starts = list(range(0, len(files), chunk))
+    if pool is None:
+        for s in starts:
+            yield s, files[s:s + chunk], [decode_frame(f) for f in files[s:s + chunk]]
+        return
+    try:
+        submit = lambda s: [pool.submit(decode_frame, f) for f in files[s:s + chunk]]
+        pending = submit(starts[0]) if starts else []
+        for k, s in enumerate(starts):
+            decoded = [f.result() for f in pending]
+            pending = submit(starts[k + 1]) if k + 1 < len(starts) else []
+            yield s, files[s:s + chunk], decoded
+    finally:
+        pool.shutdown(wait=True, cancel_futures=True)
+
+
+def host_crop(decoded, rgb_file, crop_size, image_size):
+    """prepare_image_crop (data/train_data.py:143-162) on the host: masks -> crop centre -> crop -> network size -> compose"""
+    rgb, pm, om = decoded
+    bmin, bmax = masks2bbox([pm, om])
+    center = (bmin + bmax) // 2
+    check_crop_center(center, pm.shape[1], rgb_file)
+    f = lambda a: resize_bilinear(crop(a, center, crop_size), image_size) / 255.0
+    rgb, pm, om = f(rgb), f(pm if pm.ndim == 2 else pm[..., 0]), f(om if om.ndim == 2 else om[..., 0])
+    comb = (pm > 0.5) | (om > 0.5)                                       # compose_images (data/base_data.py:252-265)
+    images = np.dstack((rgb * comb[..., None], pm, om))
+    return images.transpose(2, 0, 1).astype(np.float32), center.astype(np.float32)
+
+
 # ---- A0: the batch dict of TestDataTriplane ------------------------------------------------------------------------------------------
 class SequenceLoader:
     """Iterable of batch dicts like ``TestDataTriplane(...).get_loader(shuffle=False)``: ``images (B,8,S,S)`` = RGB * (person | object), person
     mask, object mask, three triplane renders; ``crop_center``, ``old_crop_center`` (B,2); ``resize_scale``, ``crop_scale`` (B,) = 1; ``body_center``
     (B,3); ``path`` (image files).  The triplane renders and body centres come from the SMPL-T parameters of the frames (``smplt``: packed dict with
     poses / betas / trans / frames, e.g. ``recon_<smpl_recon_name>/<seq>_k1.pkl``) through the HIP renderer and SMPL-H kernels -- the reference reads
-    the png / ply files that ``render_triplane_nr.py`` and the SMPL-T fit wrote from the same parameters (data/testdata_triplane.py:60-110)."""
+    the png / ply files that ``render_triplane_nr.py`` and the SMPL-T fit wrote from the same parameters (data/testdata_triplane.py:60-110).
+    ``device_prep=True`` builds ``images[:, :5]`` and ``crop_center`` with the HIP kernels of csrc/inputs.hip (``device_crops``) instead of numpy / torch on
+    the host; ``decode_workers=N`` decodes the images of a batch in N threads (at most 16) and already decodes batch k + 1 while batch k is consumed.  The
+    batch dicts are the same, bit for bit and in order, for every setting."""
 
-    def __init__(self, image_files, batch_size, smplt: dict, ctx, faces, image_size=512, crop_size=1200, device="cuda:0"):
+    def __init__(self, image_files, batch_size, smplt: dict, ctx, faces, image_size=512, crop_size=1200, device="cuda:0", device_prep=False,
+                 decode_workers=0):
         self.files, self.bs, self.smplt, self.ctx = list(image_files), int(batch_size), smplt, ctx
         self.image_size, self.crop_size, self.device = int(image_size), int(crop_size), device
+        self.device_prep, self.decode_workers = bool(device_prep), int(decode_workers)
         self.faces = torch.as_tensor(np.asarray(faces).astype(np.int32), device=device)
         self.frame_index = {f: i for i, f in enumerate(smplt["frames"])}
         from .triplane import TriplaneNrRenderer
@@ -131,33 +266,23 @@ class SequenceLoader:
 
     def load_crop(self, rgb_file):
         """prepare_image_crop (data/train_data.py:143-162): masks -> crop centre -> 1200-px crop -> network size -> compose"""
-        base = rgb_file[:-len(".color.jpg")]
-        pm = _load_image(_first_existing(base, [".person_mask.png", ".person_mask.jpg"]))
-        om = _load_image(_first_existing(base, [".obj_rend_mask.png", ".obj_rend_mask.jpg", ".obj_mask.png", ".obj_mask.jpg"]))
-        bmin, bmax = masks2bbox([pm, om])
-        center = (bmin + bmax) // 2
-        ih, iw = pm.shape[:2]
-        assert (center > 0).all() and center[0] < iw and center[1] < iw, f"invalid crop center value {center} for image {rgb_file}"
-        rgb = _load_image(rgb_file)
-        f = lambda a: resize_bilinear(crop(a, center, self.crop_size), self.image_size) / 255.0
-        rgb, pm, om = f(rgb), f(pm if pm.ndim == 2 else pm[..., 0]), f(om if om.ndim == 2 else om[..., 0])
-        comb = (pm > 0.5) | (om > 0.5)                                       # compose_images (data/base_data.py:252-265)
-        images = np.dstack((rgb * comb[..., None], pm, om))
-        return images.transpose(2, 0, 1).astype(np.float32), center.astype(np.float32)
+        return host_crop(decode_frame(rgb_file), rgb_file, self.crop_size, self.image_size)
 
     def __iter__(self):
         from . import ops
-        for s in range(0, len(self.files), self.bs):
-            files = self.files[s:s + self.bs]
-            crops = [self.load_crop(f) for f in files]
+        for s, files, decoded in _decoded_chunks(self.files, self.bs, self.decode_workers):
             idx = [self.frame_index[seq_and_frame(f)[1]] for f in files]
             t = lambda k: torch.as_tensor(np.asarray(self.smplt[k], np.float32)[idx], device=self.device)
             verts, _, _ = ops.smplh_forward(self.ctx.smpl, t("poses"), t("betas"), t("trans"))
             bc = ops.landmarks(self.ctx.b25, verts)[:, 8]                       # "SMPL centre" = body25 joint 8 (body_landmark.py)
             images = torch.zeros(len(files), 8, self.image_size, self.image_size, device=self.device)
-            images[:, :5] = torch.as_tensor(np.stack([c[0] for c in crops]), device=self.device)
+            if self.device_prep:
+                cc = torch.as_tensor(device_crops(decoded, files, images, self.crop_size, self.image_size))
+            else:
+                crops = [host_crop(d, f, self.crop_size, self.image_size) for d, f in zip(decoded, files)]
+                images[:, :5] = torch.as_tensor(np.stack([c[0] for c in crops]), device=self.device)
+                cc = torch.as_tensor(np.stack([c[1] for c in crops]))
             images[:, 5:8] = self.renderer.render_batch(verts, self.faces, bc)
-            cc = torch.as_tensor(np.stack([c[1] for c in crops]))
             one = torch.ones(len(files), dtype=torch.float64)                   # the default collate turns the python float 1.0 into float64
             yield {"images": images, "crop_center": cc, "old_crop_center": cc.clone(), "resize_scale": one, "crop_scale": one.clone(), "body_center": bc,
                    "path": files, "image_file": files, "kid": torch.ones(len(files), dtype=torch.long)}
