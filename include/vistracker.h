@@ -601,10 +601,20 @@ int vt_jpeg_encode(const unsigned char *rgb, int n, int H, int W, long long fram
  *   +-2^29, is written as zeros and reads nothing (crop_size < 2^28).  Only image pixels x in [max(0, tl.x), min(W - 1, br.x)) (likewise y) are read, the rest of the crop is 0.  Bilinear resize of the crop to
  *   out_size x out_size with half-pixel centres in fp32, q = clip(floor(x + 0.5), 0, 255), value = table[q] with table = 256 device floats
  *   float32(q / 255.0); rgb channels are zeroed where neither resized mask reaches 128.  Frame b is written at out + b * frame_stride floats
- *   (frame_stride >= 5 out_size^2; 8 out_size^2 for the network tensor), channels 0..4 only. */
+ *   (frame_stride >= 5 out_size^2; 8 out_size^2 for the network tensor), channels 0..4 only.
+ * vt_resize_panel_u8 (render/render_recon.py:157-159: the camera image resized to the frame's height, the left panel of every step-7 frame): n decoded uint8 RGB
+ *   images behind src (device, src_bytes bytes), frame k described by six HOST integers frames[6 k ..] = byte offset into src, full height h, full width w, first
+ *   staged column x0, staged width sw, row stride in bytes: only columns [x0, x0 + sw) of the image are there, 3 sw packed bytes per row.  Frames of different
+ *   sizes share a call.  Writes, for frame k, rows [0, H) x panel columns [0, pw) = columns [col0, col0 + pw) of the bilinear H x size resize (half-pixel centres,
+ *   fp32, q = clip(floor(v + 0.5), 0, 255): inputs.hip's header; sequence_io.resize_bilinear_hw(img, H, size)[:, col0:col0 + pw]) at out + out_off[k] (DEVICE int64
+ *   byte offsets, as vt_render_panel_u8 takes them) with out_row_stride bytes per row; no other byte of out is touched and no full-size image exists.  VT_ERR_ARG,
+ *   before anything is launched, for null pointers, non-positive sizes, rows that leave [0, src_bytes) and staged columns that do not hold every tap of the
+ *   panel's columns. */
 int vt_mask_bbox(const unsigned char *pm, const unsigned char *om, int B, int H, int W, int thres, int *box, void *stream);
 int vt_crop_resize_compose(const unsigned char *rgb, const unsigned char *pm, const unsigned char *om, int B, int H, int W, const int *corners, int crop_size,
                            int out_size, const float *table, float *out, long long frame_stride, void *stream);
+int vt_resize_panel_u8(const unsigned char *src, long long src_bytes, const long long *frames, int n, int H, int size, int col0, int pw, unsigned char *out,
+                       const long long *out_off, long long out_row_stride, void *stream);
 
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two

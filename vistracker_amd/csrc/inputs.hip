@@ -22,13 +22,29 @@
 //   compose   : comb = q_pm >= 128 or q_om >= 128 (the host's `> 0.5` on q / 255); channels 0..2 = table[comb ? q_rgb : 0], 3 = table[q_pm], 4 = table[q_om].
 //   output    : frame b at out + b * frame_stride floats, channel c at + c * S * S: channels 0..4 are written, nothing else is touched.
 //
-// MI355X mapping: two streaming kernels, VALU only, no LDS, no scratch, no float atomics.
+// CONTRACT of the step-7 camera panel (vt_resize_panel_u8; render/render_recon.py:157-159: cv2.resize of the camera image to size x H, then the panel's columns;
+// restated with integers in tests/panel_model.py).  The yardstick is sequence_io.resize_bilinear_hw(img, H, size)[:, col0:col0 + pw]:
+//   taps      : per axis in fp32, as above with n = the image's h (rows, out H) or w (columns, out size): scale = float(in) / out,
+//               src = max(scale * (d + 0.5f) - 0.5f, 0), i0 = floor(src), i1 = min(i0 + 1, in - 1), l1 = src - i0, l0 = 1 - l1.  The same device function
+//               as the crop's (its extra clamps of i0 and l1 never bind for a src computed this way).
+//   blend     : wy0 * (wx0 * p00 + wx1 * p01) + wy1 * (wx0 * p10 + wx1 * p11) per channel in fp32, in that order, no contraction into FMA: the crop's blend.
+//   rounding  : q = clip(floor(v + 0.5), 0, 255), stored as the byte it is.
+//   source    : frame k is described by six host integers: byte offset into `src`, h, w, x0, sw, row stride in bytes.  Only columns [x0, x0 + sw) of the image
+//               are behind `src` (rows of 3 sw packed bytes, row_stride apart); the entry point refuses a range that does not hold every tap of panel
+//               columns [col0, col0 + pw), or that leaves [0, src_bytes).  Frames of different sizes share a call.
+//   output    : frame k, row y in [0, H), panel column x in [0, pw) = column col0 + x of the H x size resize, at out + out_off[k] + y * out_row_stride + 3 x:
+//               straight into the frame strip, as vt_render_panel_u8 writes its panels.  No other byte is touched.
+//
+// MI355X mapping: three streaming kernels, VALU only, no LDS, no scratch, no float atomics.
 //   inp_bbox      a grid-stride pass over the two masks, 16 pixels per lane and step (one 16-byte load per mask; rows of a multiple of 16 pixels from
 //                 16-byte aligned bases) or 1 pixel per lane otherwise; per-lane min / max, wave reduction with shuffles, four integer atomics per wave
 //                 that saw a pixel.  Reads 2 H W bytes per frame.
 //   inp_crop      one thread per output pixel, all five channels: 4 taps x 5 bytes.  Lanes of a wave are 64 neighbours of an output row, so their taps
 //                 fall into two source rows of ~150 pixels: every cache line that is fetched is used by the lanes around it.  Stores are five coalesced
 //                 256-byte rows per wave.  Reads at most 5 n^2 bytes, writes 20 S^2 bytes per frame.
+//   inp_panel     one thread per output pixel, all three channels: 4 taps x 3 byte loads, 3 byte stores (plain C++: vector memory instructions only).  The
+//                 frames' descriptors travel in the kernel's arguments (up to 16 frames a launch): no descriptor upload, no synchronisation.  64 neighbours of
+//                 an output row per wave, as above.  Reads at most 3 h sw bytes, writes 3 H pw bytes per frame.
 #include "common.h"
 
 #define INP_T 256
@@ -118,15 +134,23 @@ extern "C" int vt_mask_bbox(const unsigned char *pm, const unsigned char *om, in
     return VT_OK;
 }
 
-// taps of output index d of an axis with n crop pixels (torch: area_pixel_compute_source_index + guard_index_and_lambda)
-__device__ __forceinline__ void inp_taps(int d, int n, int out_size, int &i0, int &i1, float &lam)
+// taps of output index d of an axis with n crop pixels (torch: area_pixel_compute_source_index + guard_index_and_lambda); also run on the host, where
+// vt_resize_panel_u8 checks the staged columns against it
+__host__ __device__ __forceinline__ void inp_taps(int d, int n, int out_size, int &i0, int &i1, float &lam)
 {
     const float scale = (float)n / (float)out_size;
     float src = scale * ((float)d + 0.5f) - 0.5f;
     src = src < 0.f ? 0.f : src;
-    i0 = min((int)src, n - 1);
-    i1 = min(i0 + 1, n - 1);
+    i0 = (int)src < n - 1 ? (int)src : n - 1;
+    i1 = i0 + 1 < n - 1 ? i0 + 1 : n - 1;
     lam = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
+}
+
+// blend of the four taps (a b = row i0, c d = row i1) and rounding to a grey level: the contract's `blend` and `rounding`
+__device__ __forceinline__ int inp_blend_round(float a, float b, float c, float d, float w0, float w1, float h0, float h1)
+{
+    const float x = (a * w0 + b * w1) * h0 + (c * w0 + d * w1) * h1;
+    return (int)fminf(fmaxf(floorf(x + 0.5f), 0.f), 255.f);
 }
 
 __global__ __launch_bounds__(INP_T) void inp_crop_kernel(const unsigned char *__restrict__ rgb, const unsigned char *__restrict__ pm,
@@ -170,10 +194,7 @@ __global__ __launch_bounds__(INP_T) void inp_crop_kernel(const unsigned char *__
         }
     int q[5];
 #pragma unroll
-    for (int c = 0; c < 5; c++) {
-        const float x = (v[0][0][c] * w0 + v[0][1][c] * w1) * h0 + (v[1][0][c] * w0 + v[1][1][c] * w1) * h1;
-        q[c] = (int)fminf(fmaxf(floorf(x + 0.5f), 0.f), 255.f);
-    }
+    for (int c = 0; c < 5; c++) q[c] = inp_blend_round(v[0][0][c], v[0][1][c], v[1][0][c], v[1][1][c], w0, w1, h0, h1);
     const bool comb = q[3] >= 128 || q[4] >= 128;
 #pragma unroll
     for (int c = 0; c < 3; c++) o[c * plane] = table[comb ? q[c] : 0];
@@ -190,5 +211,66 @@ extern "C" int vt_crop_resize_compose(const unsigned char *rgb, const unsigned c
     hipLaunchKernelGGL(inp_crop_kernel, dim3((out_size + 63) / 64, (out_size + 3) / 4, B), dim3(64, 4), 0, st, rgb, pm, om, H, W, corners, crop_size, out_size,
                        table, out, frame_stride);
     VT_LAUNCH_CHECK();
+    return VT_OK;
+}
+
+// ---- the camera panel of step 7 ---------------------------------------------------------------------------------------------------------------------------
+#define INP_PANEL_FRAMES 16
+struct InpPanelFrames {                                              // a launch's frames, by value in the kernel's arguments
+    long long off[INP_PANEL_FRAMES], row_stride[INP_PANEL_FRAMES];
+    int h[INP_PANEL_FRAMES], w[INP_PANEL_FRAMES], x0[INP_PANEL_FRAMES], sw[INP_PANEL_FRAMES];
+};
+
+__global__ __launch_bounds__(INP_T) void inp_panel_kernel(const unsigned char *__restrict__ src, const InpPanelFrames f, int H, int size, int col0, int pw,
+                                                          unsigned char *__restrict__ out, const long long *__restrict__ out_off, long long out_row_stride)
+{
+    const int k = blockIdx.z, px = blockIdx.x * 64 + threadIdx.x, dy = blockIdx.y * 4 + threadIdx.y;
+    if (px >= pw || dy >= H) return;
+    const int h = f.h[k], w = f.w[k], x0 = f.x0[k], sw = f.sw[k];
+    int ix0, ix1, iy0, iy1;
+    float w1, h1;
+    inp_taps(col0 + px, w, size, ix0, ix1, w1);
+    inp_taps(dy, h, H, iy0, iy1, h1);
+    const float w0 = 1.f - w1, h0 = 1.f - h1;
+    // image column -> staged column.  The entry point has checked that every tap is staged; the clamp keeps the loads inside the row whatever happens
+    const int sx0 = min(max(ix0 - x0, 0), sw - 1), sx1 = min(max(ix1 - x0, 0), sw - 1);
+    const unsigned char *r0 = src + f.off[k] + (long long)iy0 * f.row_stride[k], *r1 = src + f.off[k] + (long long)iy1 * f.row_stride[k];
+    unsigned char *o = out + out_off[k] + (long long)dy * out_row_stride + 3 * px;
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+        o[c] = (unsigned char)inp_blend_round((float)r0[3 * sx0 + c], (float)r0[3 * sx1 + c], (float)r1[3 * sx0 + c], (float)r1[3 * sx1 + c], w0, w1, h0, h1);
+}
+
+// frames: HOST, n x 6 = byte offset into src, h, w, x0, sw, row stride (bytes); out_off: DEVICE, n byte offsets into out
+extern "C" int vt_resize_panel_u8(const unsigned char *src, long long src_bytes, const long long *frames, int n, int H, int size, int col0, int pw,
+                                  unsigned char *out, const long long *out_off, long long out_row_stride, void *stream)
+{
+    VT_REQUIRE(src && frames && out && out_off && src_bytes > 0 && n > 0 && H > 0 && H <= 16384 && size > 0 && size <= 16384 && col0 >= 0 && pw > 0
+               && col0 + pw <= size && out_row_stride >= 3LL * pw, "vt_resize_panel_u8: bad argument");
+    for (int k = 0; k < n; k++) {
+        const long long off = frames[6 * k], h = frames[6 * k + 1], w = frames[6 * k + 2], x0 = frames[6 * k + 3], sw = frames[6 * k + 4], rs = frames[6 * k + 5];
+        VT_REQUIRE(h > 0 && w > 0 && h <= (1 << 20) && w <= (1 << 20) && x0 >= 0 && sw > 0 && x0 + sw <= w && rs >= 3 * sw && rs <= (1LL << 31),
+                   "vt_resize_panel_u8: frame %d: bad size (h %lld, w %lld, staged columns [%lld, %lld), row stride %lld)", k, h, w, x0, x0 + sw, rs);
+        VT_REQUIRE(off >= 0 && off <= src_bytes && (h - 1) * rs + 3 * sw <= src_bytes - off,          // h <= 2^20, rs <= 2^31: no overflow
+                   "vt_resize_panel_u8: frame %d: rows leave the %lld source bytes", k, src_bytes);
+        int lo, hi, t;
+        float lam;
+        inp_taps(col0, (int)w, size, lo, t, lam);                    // the taps grow with the output column: the first column's i0, the last one's i1
+        inp_taps(col0 + pw - 1, (int)w, size, t, hi, lam);
+        VT_REQUIRE(x0 <= lo && hi < x0 + sw, "vt_resize_panel_u8: frame %d: staged columns [%lld, %lld) do not hold the taps [%d, %d] of panel columns [%d, %d)",
+                   k, x0, x0 + sw, lo, hi, col0, col0 + pw);
+    }
+    hipStream_t st = vt_stream(stream);
+    for (int s = 0; s < n; s += INP_PANEL_FRAMES) {
+        const int g = n - s < INP_PANEL_FRAMES ? n - s : INP_PANEL_FRAMES;
+        InpPanelFrames f = {};
+        for (int k = 0; k < g; k++) {
+            const long long *d = frames + 6 * (s + k);
+            f.off[k] = d[0]; f.h[k] = (int)d[1]; f.w[k] = (int)d[2]; f.x0[k] = (int)d[3]; f.sw[k] = (int)d[4]; f.row_stride[k] = d[5];
+        }
+        hipLaunchKernelGGL(inp_panel_kernel, dim3((pw + 63) / 64, (H + 3) / 4, g), dim3(64, 4), 0, st, src, f, H, size, col0, pw, out, out_off + s,
+                           out_row_stride);
+        VT_LAUNCH_CHECK();
+    }
     return VT_OK;
 }

@@ -558,6 +558,25 @@ def crop_resize_compose(rgb, pm, om, corners, crop_size, out_size, out=None):
     return out
 
 
+def resize_panel_u8(src, frames, H, size, col0, pw, out, out_off, out_row_stride):
+    """vt_resize_panel_u8: ``src`` a uint8 device tensor holding the staged images, ``frames`` (n,6) host integers (byte offset into ``src``, h, w, first staged
+    column, staged width, row stride in bytes).  Writes rows [0, H) x columns [col0, col0 + pw) of every image's bilinear H x size resize into the uint8 device
+    tensor ``out`` at the byte offsets ``out_off`` (n,) -- an int64 device tensor, or host integers, which cost a small upload -- with ``out_row_stride`` bytes per row: ``sequence_io.resize_bilinear_hw(img, H, size)[:, col0:col0 + pw]``."""
+    d = np.ascontiguousarray(frames, dtype=np.int64).reshape(-1, 6)
+    if src.dim() == 0 or src.stride(-1) != 1 or out.device != src.device:
+        raise L.VtError("resize_panel_u8: src must have packed bytes and live on out's device")
+    off = torch.as_tensor(np.ascontiguousarray(out_off, dtype=np.int64).reshape(-1), device=out.device) if not torch.is_tensor(out_off) else out_off
+    if off.dtype != torch.int64 or off.numel() != d.shape[0]:
+        raise L.VtError(f"resize_panel_u8: {off.numel()} {off.dtype} offsets for {d.shape[0]} frames")
+    L.dptr(_u8(out, "out")); L.dptr(off)                               # device and contiguity checks; src may be a strided view
+    if not src.is_cuda or src.device.index != torch.cuda.current_device():
+        raise L.VtError("resize_panel_u8: src must be a tensor of the current device; there is no CPU route")
+    span = 1 + sum((n - 1) * st for n, st in zip(src.shape, src.stride()))          # bytes from src's first to its last element
+    L.check(L.lib().vt_resize_panel_u8(_u8(src, "src").data_ptr(), span, d.ctypes.data, d.shape[0], int(H), int(size), int(col0), int(pw), out.data_ptr(),
+                                       off.data_ptr(), int(out_row_stride), L.stream_ptr()))
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 # Adam
 # --------------------------------------------------------------------------------------------------

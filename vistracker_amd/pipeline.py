@@ -342,7 +342,7 @@ class SequencePipeline:
         return out
 
     def render(self, out, kin, rgb=None, template=None, outdir=None, start=0, end=None, interval=1, chunk=8, image_size=1200,
-               video=None, fps=30, quality=90, viz_contact=False, contact_viz_type='sphere', add_top=False):
+               video=None, fps=30, quality=90, viz_contact=False, contact_viz_type='sphere', add_top=False, device_panel=False, decode_workers=0):
         """demo step 7 (render/render_side_comp.py -s1 <recon>) on ``out["recon"]`` of ``run``: side-by-side frames [input rgb | camera 1 | camera 2]
         of the fitted SMPL-H body and object on the checkerboard ground (visualize.RendererSide2side).  ``kin``: visualize.KinectTransform of the
         sequence; ``template``: (verts, faces) of the object template; ``rgb``: None, a sequence or a callable frame index -> camera-1 image.  With
@@ -353,14 +353,16 @@ class SequencePipeline:
         ``viz_contact`` marks where the body touches the object: one sphere per touching body part (``contact_viz_type='sphere'``) or the touched
         object faces recoloured (``'face'``).  ``add_top`` (render_side_comp.py -add_top) adds the top-down strips [rgb | top view]: they go to
         ``<outdir>/top_*.png`` or ``<video stem>_top.avi`` and the call returns both results as a pair (frames, top); without ``outdir`` and
-        ``video`` the generator yields (frames, top_frames) chunk pairs."""
+        ``video`` the generator yields (frames, top_frames) chunk pairs.  ``device_panel`` / ``decode_workers``: the camera panel on the device, its
+        images (arrays, paths or device tensors) fetched and decoded one chunk ahead in a thread pool (``RendererSide2side.render_frames``)."""
         from . import visualize
         if template is None:
             raise ValueError("render() needs the object template (verts, faces)")
         r = visualize.RendererSide2side(image_size=image_size, device=self.device, contact_viz_type=contact_viz_type,
                                         part_labels=self.ctx.labels if viz_contact else None)
         gen = r.render_frames([out["recon"]], template[0], template[1], self.ctx.smpl, kin, rgb=rgb, start=start, end=end, interval=interval, chunk=chunk,
-                              on_device=video is not None, viz_contact=viz_contact, add_top=add_top)
+                              on_device=video is not None, viz_contact=viz_contact, add_top=add_top, device_panel=device_panel,
+                              decode_workers=decode_workers)
         if video is not None:
             from . import video as vid
             if not add_top:

@@ -208,16 +208,16 @@ def prepare_crops(image_files, image_size=512, crop_size=1200, device="cuda:0", 
     return images5, centers
 
 
-def _decoded_chunks(files, chunk, decode_workers):
+def _decoded_chunks(files, chunk, decode_workers, decode=decode_frame):
     """(start, files of the chunk, their decoded frames) in order; with a pool, chunk k + 1 is being decoded while chunk k is consumed"""
     pool = _decode_pool(decode_workers)
     starts = list(range(0, len(files), chunk))
     if pool is None:
         for s in starts:
-            yield s, files[s:s + chunk], [decode_frame(f) for f in files[s:s + chunk]]
+            yield s, files[s:s + chunk], [decode(f) for f in files[s:s + chunk]]
         return
     try:
-        submit = lambda s: [pool.submit(decode_frame, f) for f in files[s:s + chunk]]
+        submit = lambda s: [pool.submit(decode, f) for f in files[s:s + chunk]]
         pending = submit(starts[0]) if starts else []
         for k, s in enumerate(starts):
             decoded = [f.result() for f in pending]
@@ -225,6 +225,81 @@ def _decoded_chunks(files, chunk, decode_workers):
             yield s, files[s:s + chunk], decoded
     finally:
         pool.shutdown(wait=True, cancel_futures=True)
+
+
+# ---- the device path of step 7's camera panel (render/render_recon.py:157-159) ----------------------------------------------------------------------
+def panel_columns(w, size, cs, ce):
+    """source columns [x0, x1) of a w-pixel-wide image that the taps of columns [cs, ce) of its bilinear resize to ``size`` columns can read: the fp32 tap
+    rule of ``resize_bilinear_hw`` (csrc/inputs.hip) at the first and the last column -- the taps grow with the column -- and one column more on either side,
+    so that the range does not hang on the last bit of an fp32 product.  About (ce - cs) / size of the width."""
+    f = np.float32
+    src = lambda d: max(f(f(f(w) / f(size)) * f(f(d) + f(0.5))) - f(0.5), f(0.0))
+    lo = min(int(src(cs)), w - 1)
+    hi = min(min(int(src(ce - 1)), w - 1) + 1, w - 1)
+    return max(lo - 1, 0), min(hi + 2, w)
+
+
+def panel_sources(rgb, frames, chunk, decode_workers=0):
+    """the camera images of frames ``frames`` in chunks of ``chunk``: ``rgb`` is a sequence or a callable frame index -> (h,w,3) uint8 array, uint8 device
+    tensor or ``str`` path (decoded with ``_load_image``).  ``decode_workers`` > 0 fetches and decodes in the pool of ``decode_threads``, one chunk ahead."""
+    def fetch(i):
+        img = rgb(i) if callable(rgb) else rgb[i]
+        return _load_image(img) if isinstance(img, (str, os.PathLike)) else img
+    for _, _, images in _decoded_chunks(list(frames), int(chunk), decode_workers, decode=fetch):
+        yield images
+
+
+def stage_panels(images, size, cs, ce, pin=True):
+    """host images (h,w,3) uint8 -> (one uint8 buffer, pinned unless ``pin`` is False, with columns ``panel_columns`` of every image, rows packed, images
+    back to back; (n,6) int64 descriptors of vt_resize_panel_u8: byte offset, h, w, x0, staged width, row stride)"""
+    desc = np.zeros((len(images), 6), np.int64)
+    total = 0
+    for k, img in enumerate(images):
+        h, w = img.shape[:2]
+        x0, x1 = panel_columns(w, size, cs, ce)
+        desc[k] = (total, h, w, x0, x1 - x0, 3 * (x1 - x0))
+        total += h * 3 * (x1 - x0)
+    stage = torch.empty(total, dtype=torch.uint8, pin_memory=bool(pin))
+    host = stage.numpy()
+    for (off, h, w, x0, sw, rs), img in zip(desc, images):
+        host[off:off + h * rs].reshape(h, sw, 3)[:] = img[:, x0:x0 + sw]
+    return stage, desc
+
+
+def device_panels(images, buf, size, cs, ce):
+    """the camera panels of a chunk on the device: ``buf`` (n,H,W,3) uint8 device frames whose bytes [:, :, :ce - cs] are written with
+    ``resize_bilinear_hw(image, H, size)[:, cs:ce]`` of ``images[j]`` (csrc/inputs.hip, vt_resize_panel_u8, on the current stream).  Host arrays are staged
+    (only the columns the panel reads) into one pinned buffer and uploaded once; uint8 device tensors are read in place."""
+    from . import ops
+    n, H, W, _ = buf.shape
+    if len(images) != n:
+        raise ValueError(f"{len(images)} camera images for {n} frames")
+    host, dev = [], []
+    for j, img in enumerate(images):
+        on_dev = torch.is_tensor(img) and img.is_cuda
+        if not on_dev:
+            img = np.asarray(img)
+        if img.dtype != (torch.uint8 if on_dev else np.uint8):
+            raise ValueError(f"camera image {j}: the device panel takes uint8 images, got {img.dtype}")
+        if img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+            raise ValueError(f"camera image {j}: (h, w, 3) expected, got {tuple(img.shape)}")
+        if on_dev and (img.device != buf.device or img.stride(2) != 1 or img.stride(1) != 3 or img.stride(0) < 3 * img.shape[1]):
+            raise ValueError(f"camera image {j}: a device image needs packed pixels and rows on {buf.device}, got strides {img.stride()} on {img.device}")
+        (dev if on_dev else host).append((j, img))
+    fb, pw = H * W * 3, ce - cs
+    with torch.cuda.device(buf.device):
+        off = torch.arange(n, device=buf.device) * fb                  # the frames' byte offsets, made on the device: nothing small is uploaded
+        if host:
+            stage, desc = stage_panels([img for _, img in host], size, cs, ce)
+            staged = stage.to(buf.device, non_blocking=True)
+            js, a = [j for j, _ in host], 0
+            for b in range(1, len(js) + 1):                                # one launch per run of neighbouring frames (one, unless device tensors sit between)
+                if b == len(js) or js[b] != js[b - 1] + 1:
+                    ops.resize_panel_u8(staged, desc[a:b], H, size, cs, pw, buf, off[js[a]:js[a] + b - a], W * 3)
+                    a = b
+        for j, img in dev:                                                 # separate allocations: a launch each
+            h, w = img.shape[:2]
+            ops.resize_panel_u8(img, [[0, h, w, 0, w, img.stride(0)]], H, size, cs, pw, buf, off[j:j + 1], W * 3)
 
 
 def host_crop(decoded, rgb_file, crop_size, image_size):

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .sequence_io import resize_bilinear_hw
+from .sequence_io import device_panels, panel_sources, resize_bilinear_hw
 
 # render/nr_utils.py:282-296
 SMPL_OBJ_COLOR_LIST = [
@@ -628,7 +628,7 @@ class RendererSide2side:
         return (verts[..., 0:1] * R[0] + verts[..., 1:2] * R[1]) + verts[..., 2:3] * R[2] + T
 
     def render_frames(self, recons, temp_v, temp_f, smpl_handle, kin, rgb=None, start=0, end=None, interval=1, chunk=8, on_device=False,
-                      viz_contact=False, add_top=False):
+                      viz_contact=False, add_top=False, device_panel=False, decode_workers=0):
         """Generator of uint8 frame chunks (n, H, W, 3) for frames start:end:interval of the packed ``recons`` (dicts with poses (T,156), betas,
         trans, obj_angles (T,3,3), obj_trans, obj_scales).  ``smpl_handle``: ops.SmplhHandle of the sequence's SMPL-H model; ``kin``: KinectTransform;
         ``rgb``: None (black panel), a sequence or a callable frame index -> (h,w,3) uint8 image of camera test_id.  Every chunk renders
@@ -640,7 +640,15 @@ class RendererSide2side:
         zero-area faces, culled by the rasteriser's set-up), with 'face' every view gets its own face-colour table.  ``add_top``: the generator
         yields (frames, top_frames) pairs, top_frames (n,) + top_shape(len(recons)): [rgb panel | top-down view of every recon] over the xy ground
         (render_side_comp.py:52-66, render_recon.py:172-178).  Every frame is written: the reference loses the first top-view frame while it opens
-        its second writer, which is not copied."""
+        its second writer, which is not copied.
+
+        ``device_panel=True`` builds the camera panel with vt_resize_panel_u8 (csrc/inputs.hip) instead of ``resize_bilinear_hw`` on the host, frame by
+        frame: ``rgb`` may then also give ``str`` paths (decoded with the loader's ``_load_image``) or uint8 device tensors (read in place); host images
+        of a chunk are staged -- only the columns the panel reads -- into one pinned buffer and uploaded once.  ``decode_workers=N`` fetches and decodes
+        the images of the next chunk in a pool of at most 16 threads while this one is rendered.  The frames are the default path's wherever the fp32
+        blends are exact (e.g. 96 x 128 images for image_size 64), elsewhere within one grey level at pixels whose blend sits on a rounding boundary."""
+        if decode_workers > 0 and not device_panel:
+            raise ValueError("decode_workers needs device_panel=True")
         dev = torch.device(self.device)
         size = self.image_size
         cs, ce = self.get_xcuts(size)
@@ -671,10 +679,12 @@ class RendererSide2side:
             Ht, Wt, _ = self.top_shape(n)
             cut = H - Ht
         kids = [self.test_id, self.test_id + 1]
+        sources = panel_sources(rgb, frames, chunk, decode_workers) if device_panel and rgb is not None else None
         with torch.cuda.device(dev):
             for c0 in range(0, len(frames), chunk):
                 idx = frames[c0:c0 + chunk]
                 nc = len(idx)
+                images = next(sources) if sources is not None else None          # with a pool, the next chunk's are being decoded from here on
                 ii = torch.as_tensor(idx, device=dev)
                 per_recon, per_colors = [], []
                 for d in recons:
@@ -703,7 +713,9 @@ class RendererSide2side:
                 b = torch.arange(nc * 2 * n, device=dev)
                 off = (b // (2 * n)) * (H * W * 3) + (1 + b % (2 * n)) * (pw * 3)
                 panels_u8(out["rgb"], buf, off, 0, H, cs, pw, W * 3)
-                if rgb is not None:
+                if images is not None:
+                    device_panels(images, buf, size, cs, ce)
+                elif rgb is not None:
                     for j, i in enumerate(idx):
                         img = rgb(i) if callable(rgb) else rgb[i]
                         img = resize_bilinear_hw(np.asarray(img), H, size)[:, cs:ce]
