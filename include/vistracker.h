@@ -616,6 +616,29 @@ int vt_crop_resize_compose(const unsigned char *rgb, const unsigned char *pm, co
 int vt_resize_panel_u8(const unsigned char *src, long long src_bytes, const long long *frames, int n, int H, int size, int col0, int pw, unsigned char *out,
                        const long long *out_off, long long out_row_stride, void *stream);
 
+/* ---- the fit on the camera image and its score on the masks (demo step 7; overlay.hip's header holds both contracts, tests/overlay_model.py restates them) -----
+ * The reference declares -am / --add_mask (render/render_recon.py:346) and never reads it; it has no ground-truth-free score.  Both rules are this project's.
+ *
+ * vt_overlay_panel_u8: rgb (B,S,S,3), alpha (B,S,S) of a vt_render_rgb call without a static layer and with background (0,0,0) (rgb premultiplied by coverage);
+ *   crop rows [row0, row0 + nrows) x columns [col0, col0 + ncols) as in vt_render_panel_u8.  View b reads the uint8 panel at out + src_off[b] and writes the panel
+ *   at out + dst_off[b] (DEVICE int64 byte offsets, rows out_row_stride bytes apart; src_off[b] == dst_off[b] is allowed, no other overlap is).  Per pixel and
+ *   channel c in fp32, in this order: a = opacity * alpha, v = (255 * opacity) * min(max(rgb_c, 0), 1) + (1 - a) * p, q = clip(floor(v + 0.5), 0, 255) with p the
+ *   source byte: q == p bit for bit where alpha == 0 and rgb == 0, and for opacity == 0.  No byte outside the destination panels is written.  VT_ERR_ARG before
+ *   any launch for null pointers, non-positive sizes, a crop outside [0, S), out_row_stride < 3 ncols, opacity outside [0, 1].
+ * vt_mask_score: fidx (B,is,is) int32 = face_index of a vt_render_rgb call without a static layer over F faces: doubled id d -> face d < F ? d : d - F, -1 and
+ *   ids >= 2 F -> none; faces < nf_body are body, faces < nf_body + nf_obj object, later ones (contact spheres) neither.  Masks: uint8 behind pm (person) and om
+ *   (object; may be the same buffer), view b described by eight HOST integers frames[8 b ..] = byte offset of its person mask in pm, of its object mask in om, h,
+ *   w, pixel stride and row stride of the person mask, pixel stride and row stride of the object mask (pixel stride C reads channel 0 of an (h,w,C) mask); all
+ *   checked against pm_bytes / om_bytes before anything is launched.  A pixel is on when its value > thres.  Raster sample (yi, xi), yi < rows, xi < is, reads
+ *   mask pixel sy = ((2 yi + 1) h) / (2 rows), sx = ((2 xi + 1) w) / (2 is) (integer division: nearest neighbour at half-pixel centres).  count (B,2,4) int32,
+ *   zeroed by the call on the stream; class 0 = body against pm, class 1 = object against om: [0] owner is the class and the mask is on, [1] owner is the class,
+ *   [2] the mask is on, [3] the mask is on and the owner is the other class.  Integer arithmetic and integer atomics only (at most 8 per workgroup, at most 64
+ *   workgroups per view): bit-identical from run to run, independent of B and of a view's place in the batch. */
+int vt_overlay_panel_u8(const float *rgb, const float *alpha, int B, int size, int row0, int nrows, int col0, int ncols, unsigned char *out,
+                        const long long *src_off, const long long *dst_off, long long out_row_stride, float opacity, void *stream);
+int vt_mask_score(const int *fidx, int B, int is, int rows, int F, int nf_body, int nf_obj, const unsigned char *pm, long long pm_bytes, const unsigned char *om,
+                  long long om_bytes, const long long *frames, int thres, int *count, void *stream);
+
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two
  * workgroups of 256 threads per CU, non-trivial operands), out[1] = shader clock sustained during it (MHz: s_memtime against the 100 MHz s_memrealtime),

@@ -143,6 +143,8 @@ SIGNATURES = {
     "vt_mask_bbox": (ci, [fp, fp, ci, ci, ci, ci, fp, vp]),
     "vt_crop_resize_compose": (ci, [fp, fp, fp, ci, ci, ci, fp, ci, ci, fp, fp, C.c_longlong, vp]),
     "vt_resize_panel_u8": (ci, [fp, C.c_longlong, vp, ci, ci, ci, ci, ci, fp, fp, C.c_longlong, vp]),
+    "vt_overlay_panel_u8": (ci, [fp, fp, ci, ci, ci, ci, ci, ci, fp, fp, fp, C.c_longlong, cf, vp]),
+    "vt_mask_score": (ci, [fp, ci, ci, ci, ci, ci, ci, fp, C.c_longlong, fp, C.c_longlong, vp, ci, fp, vp]),
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
 }

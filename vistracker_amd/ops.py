@@ -578,6 +578,56 @@ def resize_panel_u8(src, frames, H, size, col0, pw, out, out_off, out_row_stride
 
 
 # --------------------------------------------------------------------------------------------------
+# the fit on the camera image, and its score on the masks (csrc/overlay.hip)
+# --------------------------------------------------------------------------------------------------
+def _offsets(off, n, device, name):
+    off = torch.as_tensor(np.ascontiguousarray(off, dtype=np.int64).reshape(-1), device=device) if not torch.is_tensor(off) else off
+    if off.dtype != torch.int64 or off.numel() != n:
+        raise L.VtError(f"{name}: {off.numel()} {off.dtype} offsets for {n} views")
+    return off
+
+
+def overlay_panel_u8(rgb, alpha, out, src_off, dst_off, row0, nrows, col0, ncols, out_row_stride, opacity):
+    """vt_overlay_panel_u8: rgb (B,S,S,3), alpha (B,S,S) of a render without a static layer over background 0; view b's crop rows [row0, row0 + nrows) x columns
+    [col0, col0 + ncols) is composited at ``opacity`` over the uint8 panel at byte offset ``src_off[b]`` of the device tensor ``out`` and written at ``dst_off[b]``
+    (int64 device tensors, or host integers, which cost a small upload; equal offsets = in place), rows ``out_row_stride`` bytes apart."""
+    B, S = rgb.shape[0], rgb.shape[1]
+    if tuple(rgb.shape) != (B, S, S, 3) or tuple(alpha.shape) != (B, S, S) or rgb.dtype != torch.float32 or alpha.dtype != torch.float32:
+        raise L.VtError(f"overlay_panel_u8: rgb {tuple(rgb.shape)} {rgb.dtype}, alpha {tuple(alpha.shape)} {alpha.dtype}")
+    so, do = _offsets(src_off, B, rgb.device, "overlay_panel_u8"), _offsets(dst_off, B, rgb.device, "overlay_panel_u8")
+    L.check(L.lib().vt_overlay_panel_u8(L.dptr(rgb), L.dptr(alpha), B, S, int(row0), int(nrows), int(col0), int(ncols), L.dptr(_u8(out, "out")), L.dptr(so),
+                                        L.dptr(do), int(out_row_stride), float(opacity), L.stream_ptr()))
+    return out
+
+
+def _span(t):
+    """bytes from a uint8 tensor's first to its last element"""
+    return 1 + sum((n - 1) * st for n, st in zip(t.shape, t.stride()))
+
+
+def mask_score(fidx, rows, F, nf_body, nf_obj, pm, om, frames, thres=127, count=None):
+    """vt_mask_score: fidx (B,is,is) int32 owner maps of a render without a static layer over ``F`` faces (the first ``nf_body`` body, the next ``nf_obj`` object);
+    ``pm`` / ``om`` uint8 device tensors holding the person / object masks (may be the same tensor, may be strided views), ``frames`` (B,8) host integers per view:
+    byte offset of the person mask in ``pm``, of the object mask in ``om``, h, w, pixel and row stride of the person mask, of the object mask.  Scores raster rows
+    [0, rows).  -> count (B,2,4) int32 device tensor (written into ``count`` when given): per class (body against pm, object against om) inter, fit, mask, hidden."""
+    B, s = fidx.shape[0], fidx.shape[1]
+    d = np.ascontiguousarray(frames, dtype=np.int64).reshape(-1, 8)
+    if fidx.dim() != 3 or fidx.shape[2] != s or fidx.dtype != torch.int32 or d.shape[0] != B:
+        raise L.VtError(f"mask_score: fidx {tuple(fidx.shape)} {fidx.dtype} with {d.shape[0]} mask descriptors")
+    for m, name in ((pm, "pm"), (om, "om")):
+        if not m.is_cuda or m.device != fidx.device or m.device.index != torch.cuda.current_device() or m.numel() == 0:
+            raise L.VtError(f"mask_score: {name} must be a non-empty tensor of fidx's (the current) device; there is no CPU route")
+        _u8(m, name)
+    if count is None:
+        count = torch.empty(B, 2, 4, dtype=torch.int32, device=fidx.device)
+    elif count.dtype != torch.int32 or tuple(count.shape) != (B, 2, 4):
+        raise L.VtError(f"mask_score: count {tuple(count.shape)} {count.dtype} for {B} views")
+    L.check(L.lib().vt_mask_score(L.dptr(fidx), B, s, int(rows), int(F), int(nf_body), int(nf_obj), pm.data_ptr(), _span(pm), om.data_ptr(), _span(om),
+                                  d.ctypes.data, int(thres), L.dptr(count), L.stream_ptr()))
+    return count
+
+
+# --------------------------------------------------------------------------------------------------
 # Adam
 # --------------------------------------------------------------------------------------------------
 class FusedAdam:

@@ -342,7 +342,8 @@ class SequencePipeline:
         return out
 
     def render(self, out, kin, rgb=None, template=None, outdir=None, start=0, end=None, interval=1, chunk=8, image_size=1200,
-               video=None, fps=30, quality=90, viz_contact=False, contact_viz_type='sphere', add_top=False, device_panel=False, decode_workers=0):
+               video=None, fps=30, quality=90, viz_contact=False, contact_viz_type='sphere', add_top=False, device_panel=False, decode_workers=0,
+               overlay=False, overlay_opacity=0.6):
         """demo step 7 (render/render_side_comp.py -s1 <recon>) on ``out["recon"]`` of ``run``: side-by-side frames [input rgb | camera 1 | camera 2]
         of the fitted SMPL-H body and object on the checkerboard ground (visualize.RendererSide2side).  ``kin``: visualize.KinectTransform of the
         sequence; ``template``: (verts, faces) of the object template; ``rgb``: None, a sequence or a callable frame index -> camera-1 image.  With
@@ -354,7 +355,8 @@ class SequencePipeline:
         object faces recoloured (``'face'``).  ``add_top`` (render_side_comp.py -add_top) adds the top-down strips [rgb | top view]: they go to
         ``<outdir>/top_*.png`` or ``<video stem>_top.avi`` and the call returns both results as a pair (frames, top); without ``outdir`` and
         ``video`` the generator yields (frames, top_frames) chunk pairs.  ``device_panel`` / ``decode_workers``: the camera panel on the device, its
-        images (arrays, paths or device tensors) fetched and decoded one chunk ahead in a thread pool (``RendererSide2side.render_frames``)."""
+        images (arrays, paths or device tensors) fetched and decoded one chunk ahead in a thread pool (``RendererSide2side.render_frames``).  ``overlay`` (needs
+        ``rgb``) adds, behind the camera panel, one panel per recon with the fit drawn on the camera image at ``overlay_opacity``."""
         from . import visualize
         if template is None:
             raise ValueError("render() needs the object template (verts, faces)")
@@ -362,7 +364,7 @@ class SequencePipeline:
                                         part_labels=self.ctx.labels if viz_contact else None)
         gen = r.render_frames([out["recon"]], template[0], template[1], self.ctx.smpl, kin, rgb=rgb, start=start, end=end, interval=interval, chunk=chunk,
                               on_device=video is not None, viz_contact=viz_contact, add_top=add_top, device_panel=device_panel,
-                              decode_workers=decode_workers)
+                              decode_workers=decode_workers, overlay=overlay, overlay_opacity=overlay_opacity)
         if video is not None:
             from . import video as vid
             if not add_top:
@@ -378,6 +380,17 @@ class SequencePipeline:
             paths += visualize.write_frames([fr], outdir, start=start + len(paths))
             tops += visualize.write_frames([top], outdir, start=start + len(tops), prefix="top")
         return paths, tops
+
+    def mask_scores(self, out, kin, masks, template, start=0, end=None, interval=1, chunk=8, image_size=1200, decode_workers=0):
+        """Which frames of ``out["recon"]`` went wrong, without ground truth: per frame the overlap of what camera 1 sees of the fitted body and object with the
+        frame's person and object masks (visualize.RendererSide2side.mask_scores, csrc/overlay.hip).  ``masks``: a sequence or a callable frame index -> a
+        (person, object) pair of uint8 arrays or device tensors, or the path of the frame's colour image (``sequence_io.decode_masks`` finds its masks);
+        ``template``: (verts, faces) of the object template.  -> {"count": (n_frames, 1, 2, 4) int32 inter, fit, mask, hidden per class (body, object), "iou":
+        (n_frames, 1, 2) float64, nan where neither the fit nor the mask has a sample}."""
+        from . import visualize
+        r = visualize.RendererSide2side(image_size=image_size, device=self.device)
+        return r.mask_scores([out["recon"]], template[0], template[1], self.ctx.smpl, kin, masks, start=start, end=end, interval=interval, chunk=chunk,
+                             decode_workers=decode_workers)
 
     def contacts(self, out, template, chunk=64):
         """Which body part touches the object in which frame of ``out["recon"]`` (visualize.ContactVisualizer.regions at the renderer's threshold of

@@ -114,11 +114,18 @@ def resize_bilinear_hw(img: np.ndarray, height: int, width: int) -> np.ndarray:
 MAX_DECODE_WORKERS = 16
 
 
-def decode_frame(rgb_file):
-    """the three images of a frame as PIL decodes them: rgb (H,W,3), person mask, object mask (masks as stored: (H,W) or (H,W,C))"""
+def decode_masks(rgb_file):
+    """the two masks of the frame whose colour image is ``rgb_file`` (``<frame>/k1.color.jpg``; it is not opened), found by the loader's rule and as PIL decodes
+    them: person mask, object mask ((H,W) or (H,W,C) as stored)"""
     base = rgb_file[:-len(".color.jpg")]
     pm = _load_image(_first_existing(base, [".person_mask.png", ".person_mask.jpg"]))
     om = _load_image(_first_existing(base, [".obj_rend_mask.png", ".obj_rend_mask.jpg", ".obj_mask.png", ".obj_mask.jpg"]))
+    return pm, om
+
+
+def decode_frame(rgb_file):
+    """the three images of a frame as PIL decodes them: rgb (H,W,3), person mask, object mask (masks as stored: (H,W) or (H,W,C))"""
+    pm, om = decode_masks(rgb_file)
     return _load_image(rgb_file), pm, om
 
 
@@ -300,6 +307,79 @@ def device_panels(images, buf, size, cs, ce):
         for j, img in dev:                                                 # separate allocations: a launch each
             h, w = img.shape[:2]
             ops.resize_panel_u8(img, [[0, h, w, 0, w, img.stride(0)]], H, size, cs, pw, buf, off[j:j + 1], W * 3)
+
+
+# ---- the masks of step 7's score (csrc/overlay.hip, vt_mask_score) ------------------------------------------------------------------------------------
+def mask_sources(masks, frames, chunk, decode_workers=0):
+    """the (person, object) mask pairs of frames ``frames`` in chunks of ``chunk``: ``masks`` is a sequence or a callable frame index -> pair of uint8 arrays,
+    pair of uint8 device tensors, or the ``str`` path of the frame's colour image (its masks are found and decoded by ``decode_masks``).  ``decode_workers`` > 0
+    fetches and decodes in the pool of ``decode_threads``, one chunk ahead."""
+    def fetch(i):
+        m = masks(i) if callable(masks) else masks[i]
+        return decode_masks(os.fspath(m)) if isinstance(m, (str, os.PathLike)) else m
+    for _, _, pairs in _decoded_chunks(list(frames), int(chunk), decode_workers, decode=fetch):
+        yield pairs
+
+
+def stage_masks(pairs, pin=True):
+    """host mask pairs ((h,w) or (h,w,C) uint8, channel 0 counts as in ``masks2bbox``) -> (one uint8 buffer, pinned unless ``pin`` is False, with channel 0 of
+    every mask, rows packed, masks back to back; (n,8) int64 descriptors of vt_mask_score: byte offsets of the person and the object mask, h, w, pixel and row
+    stride of either)"""
+    desc = np.zeros((len(pairs), 8), np.int64)
+    total = 0
+    for k, (pm, om) in enumerate(pairs):
+        h, w = pm.shape[:2]
+        desc[k] = (total, total + h * w, h, w, 1, w, 1, w)
+        total += 2 * h * w
+    stage = torch.empty(total, dtype=torch.uint8, pin_memory=bool(pin))
+    host = stage.numpy()
+    for (po, oo, h, w, _, _, _, _), (pm, om) in zip(desc, pairs):
+        host[po:po + h * w].reshape(h, w)[:] = pm if pm.ndim == 2 else pm[..., 0]
+        host[oo:oo + h * w].reshape(h, w)[:] = om if om.ndim == 2 else om[..., 0]
+    return stage, desc
+
+
+def device_mask_scores(pairs, fidx, rows, F, nf_body, nf_obj, n_recons, thres=127):
+    """vt_mask_score of a chunk: ``pairs`` one (person, object) mask pair per frame, ``fidx`` (len(pairs) * n_recons, is, is) owner maps, frame-major: the
+    ``n_recons`` views of a frame share its masks.  Host pairs are staged into one pinned buffer and uploaded once; pairs of uint8 device tensors are read in
+    place.  -> count (len(pairs) * n_recons, 2, 4) int32 device tensor, nothing synchronised."""
+    from . import ops
+    nf, n = len(pairs), int(n_recons)
+    if fidx.shape[0] != nf * n:
+        raise ValueError(f"{nf} mask pairs for {fidx.shape[0]} owner maps of {n} recons a frame")
+    host, dev = [], []
+    for j, pair in enumerate(pairs):
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            raise ValueError(f"masks of frame {j}: a (person, object) pair expected")
+        on_dev = [torch.is_tensor(m) and m.is_cuda for m in pair]
+        if on_dev[0] != on_dev[1]:
+            raise ValueError(f"masks of frame {j}: both on the device or both on the host")
+        pair = tuple(pair) if on_dev[0] else tuple(np.asarray(m) for m in pair)
+        for m in pair:
+            if m.dtype != (torch.uint8 if on_dev[0] else np.uint8):
+                raise ValueError(f"masks of frame {j}: uint8 expected, got {m.dtype}")
+            if m.ndim not in (2, 3) or min(m.shape) < 1 or tuple(m.shape[:2]) != tuple(pair[0].shape[:2]):
+                raise ValueError(f"masks of frame {j}: two (h,w) or (h,w,C) masks of one size expected, got {tuple(pair[0].shape)} and {tuple(pair[1].shape)}")
+            if on_dev[0] and (m.device != fidx.device or m.stride(1) < (m.shape[2] if m.ndim == 3 else 1) or m.stride(0) < m.shape[1] * m.stride(1)
+                              or (m.ndim == 3 and m.stride(2) != 1)):
+                raise ValueError(f"masks of frame {j}: a device mask needs rows and pixels that do not overlap on {fidx.device}, got strides {m.stride()} on {m.device}")
+        (dev if on_dev[0] else host).append((j, pair))
+    count = torch.empty(nf * n, 2, 4, dtype=torch.int32, device=fidx.device)
+    with torch.cuda.device(fidx.device):
+        if host:
+            stage, desc = stage_masks([p for _, p in host])
+            staged = stage.to(fidx.device, non_blocking=True)
+            js, a = [j for j, _ in host], 0
+            for b in range(1, len(js) + 1):                                # one call per run of neighbouring frames (one, unless device pairs sit between)
+                if b == len(js) or js[b] != js[b - 1] + 1:
+                    lo, hi = js[a] * n, (js[a] + b - a) * n
+                    ops.mask_score(fidx[lo:hi], rows, F, nf_body, nf_obj, staged, staged, np.repeat(desc[a:b], n, 0), thres, count=count[lo:hi])
+                    a = b
+        for j, (pm, om) in dev:                                            # separate allocations: a call each
+            h, w = pm.shape[:2]
+            d = [[0, 0, h, w, pm.stride(1), pm.stride(0), om.stride(1), om.stride(0)]] * n
+            ops.mask_score(fidx[j * n:(j + 1) * n], rows, F, nf_body, nf_obj, pm, om, d, thres, count=count[j * n:(j + 1) * n])
+    return count
 
 
 def host_crop(decoded, rgb_file, crop_size, image_size):

@@ -8,7 +8,8 @@ an ``nr.Renderer``.  The ground is rendered as a *static layer*: set up, binned 
 resolve (bit-identical to rendering the concatenated scene).  The video is ``video.write_video`` (Motion-JPEG AVI, GPU JPEG encoder; frames from
 ``render_frames(..., on_device=True)`` never leave the device).  Contacts (``viz_contact``: one sphere per touching body part, or the touched object
 faces recoloured) come from ``csrc/contact.hip`` through ``ContactVisualizer``; the ``-add_top`` view is the same rasteriser behind a look-at
-transform, over the ``xy`` ground.  Not here: ``cv2.putText`` labels (no cv2), ``-w`` Procrustes alignment, PHOSA, lens distortion.
+transform, over the ``xy`` ground.  ``overlay`` draws the fit on the camera image and ``mask_scores`` counts its overlap with the input masks
+(``csrc/overlay.hip``).  Not here: ``cv2.putText`` labels (no cv2), ``-w`` Procrustes alignment, PHOSA, lens distortion.
 """
 from __future__ import annotations
 
@@ -23,7 +24,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .sequence_io import device_panels, panel_sources, resize_bilinear_hw
+from .sequence_io import device_mask_scores, device_panels, mask_sources, panel_sources, resize_bilinear_hw
 
 # render/nr_utils.py:282-296
 SMPL_OBJ_COLOR_LIST = [
@@ -602,9 +603,9 @@ class RendererSide2side:
     def get_xcuts(self, image_size):
         return int(self.xcut_start * image_size), int(self.xcut_end * image_size)
 
-    def frame_shape(self, n_recons):
+    def frame_shape(self, n_recons, overlay=False):
         cs, ce = self.get_xcuts(self.image_size)
-        return int(self.aspect_ratio * self.image_size), (ce - cs) * (1 + 2 * n_recons), 3
+        return int(self.aspect_ratio * self.image_size), (ce - cs) * (1 + (3 if overlay else 2) * n_recons), 3
 
     @property
     def ground_xy(self):
@@ -627,8 +628,100 @@ class RendererSide2side:
         R = torch.as_tensor(self.top_R, device=verts.device); T = torch.as_tensor(self.top_T, device=verts.device)
         return (verts[..., 0:1] * R[0] + verts[..., 1:2] * R[1]) + verts[..., 2:3] * R[2] + T
 
+    def _scene(self, temp_v, temp_f, smpl_handle, viz_contact=False):
+        """what every chunk of a sequence shares: the face list [SMPL-H, object (, 14 contact spheres)] and its colours on the device, the object template"""
+        dev = torch.device(self.device)
+        temp_f = np.asarray(temp_f)
+        smpl_f = np.asarray(smpl_handle.faces)
+        nvs = 6890
+        faces = np.concatenate([smpl_f, temp_f + nvs], 0).astype(np.int32)
+        colors = np.concatenate([np.tile(np.asarray(self.nrwrapper.colors[0], np.float32), (len(smpl_f), 1)),
+                                 np.tile(np.asarray(self.nrwrapper.colors[1], np.float32), (len(temp_f), 1))], 0)
+        tv = torch.as_tensor(np.asarray(temp_v), dtype=torch.float32, device=dev)
+        nv_mesh = nvs + tv.shape[0]
+        cviz = self.nrwrapper.contacts() if viz_contact else None
+        spheres = viz_contact and self.nrwrapper.contact_viz_type == 'sphere'
+        if spheres:
+            sf, sc = cviz.sphere_faces_colors(nv_mesh)
+            faces, colors = np.concatenate([faces, sf], 0), np.concatenate([colors, sc], 0)
+        return SimpleNamespace(temp_f=temp_f, nf_body=len(smpl_f), nf_obj=len(temp_f), tv=tv, nv_mesh=nv_mesh, cviz=cviz, spheres=spheres,
+                               faces_d=torch.as_tensor(faces, device=dev), colors_d=torch.as_tensor(colors, device=dev))
+
+    def _chunk_meshes(self, sc, recons, smpl_handle, idx):
+        """frames ``idx`` of every recon in packed coordinates: per recon (len(idx), NV, 3) [SMPL-H, object (, spheres)] vertices, and, for contact-coloured
+        faces, per recon (len(idx), NF, 3) colour tables (else an empty list)"""
+        dev = sc.tv.device
+        nc = len(idx)
+        ii = torch.as_tensor(idx, device=dev)
+        per_recon, per_colors = [], []
+        for d in recons:
+            T = len(d["poses"])
+            g = lambda k, w: torch.as_tensor(np.asarray(d[k], np.float32).reshape(T, w), device=dev)[ii].contiguous()
+            sv, _, _ = ops.smplh_forward(smpl_handle, g("poses", 156), g("betas", 10), g("trans", 3))
+            R = g("obj_angles", 9).reshape(nc, 3, 3); t = g("obj_trans", 3); s = g("obj_scales", 1)
+            ov = (sc.tv[None] @ R + t[:, None]) * s[:, :, None]
+            block = [sv.detach(), ov]
+            if sc.cviz is not None:
+                reg = sc.cviz.regions(block[0], ov)
+                if sc.spheres:
+                    block.append(sc.cviz.spheres(reg))
+                else:
+                    per_colors.append(sc.cviz.face_colors(reg["part"], sc.temp_f, sc.nf_body, sc.colors_d))
+            per_recon.append(torch.cat(block, 1))
+        return per_recon, per_colors
+
+    def fit_views(self, sc, per_recon, per_colors, kin):
+        """the camera-``test_id`` view of every (frame, recon) of a chunk WITHOUT the ground: no static layer, background 0, the chunk's own face list (contact
+        spheres or per-view colours included) -> vt_render_rgb's dict, views frame-major (frame j, recon r at j * n + r): rgb premultiplied by coverage, alpha,
+        face_index (the owner map vt_mask_score reads).  What ``overlay`` composites and ``mask_scores`` scores."""
+        renderer = self.nrwrapper.front_renderer
+        bare = RenderParams(**{**vars(renderer), "background_color": [0.0, 0.0, 0.0]})
+        views = torch.stack([kin.world2local_torch(v, self.test_id) for v in per_recon], 1)               # (nc, n, NV, 3)
+        nc, n = views.shape[0], views.shape[1]
+        views = views.reshape(nc * n, views.shape[-2], 3).contiguous()
+        if bool((views[:, :sc.nv_mesh, 2].amin() < 0).item()):
+            raise ValueError("a mesh lies behind the camera (render_side_comp.py:86-90 allows that for PHOSA only)")
+        cols = torch.stack(per_colors, 1).reshape(nc * n, -1, 3) if per_colors else sc.colors_d
+        return self.nrwrapper.raster.render(views, sc.faces_d, cols, bare, static=None, want_index=True)
+
+    def mask_scores(self, recons, temp_v, temp_f, smpl_handle, kin, masks, start=0, end=None, interval=1, chunk=8, decode_workers=0):
+        """Which frames went wrong, without ground truth: the overlap of the fit's owner map (``fit_views``: what is VISIBLE of the body and of the object from
+        camera ``test_id``) with the frame's person and object masks, counted by vt_mask_score (csrc/overlay.hip) over the panel's rows [0, H) of the render.
+        ``masks``: a sequence or a callable frame index -> a (person, object) pair of uint8 arrays ((h,w) or (h,w,C), channel 0 counts, on when > 127), the ``str``
+        path of the frame's colour image (its masks are found and decoded by ``sequence_io.decode_masks``) or a pair of uint8 device tensors (read in place).
+        Host masks of a chunk go through one pinned buffer and one upload; ``decode_workers=N`` fetches and decodes the next chunk's in the loader's pool (at most
+        16 threads).  One synchronisation per chunk, the read-back of the counts.
+        -> {"count": (n_frames, n_recons, 2, 4) int32: per class (0 body against the person mask, 1 object against the object mask) inter, fit, mask, hidden (the
+        mask is on and the OTHER class owns the sample: discounts occlusion when the object mask is a full, unoccluded rendering); "iou": (n_frames, n_recons, 2)
+        float64 inter / (fit + mask - inter), nan where that union is 0}."""
+        dev = torch.device(self.device)
+        size = self.image_size
+        H = self.frame_shape(len(recons))[0]
+        n = len(recons)
+        T = len(recons[0]["poses"])
+        end = T if end is None else end
+        frames = list(range(start, end, interval))
+        sc = self._scene(temp_v, temp_f, smpl_handle)
+        F = int(sc.faces_d.shape[0])
+        sources = mask_sources(masks, frames, chunk, decode_workers)
+        counts = []
+        with torch.cuda.device(dev):
+            for c0 in range(0, len(frames), chunk):
+                idx = frames[c0:c0 + chunk]
+                pairs = next(sources)                                               # with a pool, the next chunk's are being decoded from here on
+                per_recon, per_colors = self._chunk_meshes(sc, recons, smpl_handle, idx)
+                fidx = self.fit_views(sc, per_recon, per_colors, kin)["face_index"]
+                rows = H * fidx.shape[1] // size
+                cnt = device_mask_scores(pairs, fidx, rows, F, sc.nf_body, sc.nf_obj, n)
+                counts.append(cnt.cpu().numpy().reshape(len(idx), n, 2, 4))       # the one synchronisation of the chunk
+        count = np.concatenate(counts) if counts else np.zeros((0, n, 2, 4), np.int32)
+        c = count.astype(np.int64)
+        union = c[..., 1] + c[..., 2] - c[..., 0]
+        iou = np.where(union > 0, c[..., 0] / np.maximum(union, 1), np.nan)
+        return {"count": count, "iou": iou}
+
     def render_frames(self, recons, temp_v, temp_f, smpl_handle, kin, rgb=None, start=0, end=None, interval=1, chunk=8, on_device=False,
-                      viz_contact=False, add_top=False, device_panel=False, decode_workers=0):
+                      viz_contact=False, add_top=False, device_panel=False, decode_workers=0, overlay=False, overlay_opacity=0.6):
         """Generator of uint8 frame chunks (n, H, W, 3) for frames start:end:interval of the packed ``recons`` (dicts with poses (T,156), betas,
         trans, obj_angles (T,3,3), obj_trans, obj_scales).  ``smpl_handle``: ops.SmplhHandle of the sequence's SMPL-H model; ``kin``: KinectTransform;
         ``rgb``: None (black panel), a sequence or a callable frame index -> (h,w,3) uint8 image of camera test_id.  Every chunk renders
@@ -646,13 +739,22 @@ class RendererSide2side:
         frame: ``rgb`` may then also give ``str`` paths (decoded with the loader's ``_load_image``) or uint8 device tensors (read in place); host images
         of a chunk are staged -- only the columns the panel reads -- into one pinned buffer and uploaded once.  ``decode_workers=N`` fetches and decodes
         the images of the next chunk in a pool of at most 16 threads while this one is rendered.  The frames are the default path's wherever the fp32
-        blends are exact (e.g. 96 x 128 images for image_size 64), elsewhere within one grey level at pixels whose blend sits on a rounding boundary."""
+        blends are exact (e.g. 96 x 128 images for image_size 64), elsewhere within one grey level at pixels whose blend sits on a rounding boundary.
+
+        ``overlay=True`` (needs ``rgb``) draws the fit ON the camera image: a frame becomes [rgb | overlay recon_1 .. recon_n | camera kid recon_1 .. | camera
+        kid + 1 recon_1 ..], every overlay panel the frame's own camera panel with the ground-free camera-kid render of that recon (``fit_views``) composited at
+        ``overlay_opacity`` by vt_overlay_panel_u8 (csrc/overlay.hip) -- the panel is that camera's image and the render uses that camera's intrinsics, so
+        the two are pixel-aligned.  Every other panel, and the top strips, keep their bytes."""
         if decode_workers > 0 and not device_panel:
             raise ValueError("decode_workers needs device_panel=True")
+        if overlay and rgb is None:
+            raise ValueError("overlay=True needs the camera images (rgb): there is nothing to draw the fit on")
+        if overlay and not 0.0 <= float(overlay_opacity) <= 1.0:
+            raise ValueError(f"overlay_opacity {overlay_opacity} outside [0, 1]")
         dev = torch.device(self.device)
         size = self.image_size
         cs, ce = self.get_xcuts(size)
-        H, W, _ = self.frame_shape(len(recons))
+        H, W, _ = self.frame_shape(len(recons), overlay)
         pw = ce - cs
         n = len(recons)
         T = len(recons[0]["poses"])
@@ -660,20 +762,9 @@ class RendererSide2side:
         frames = list(range(start, end, interval))
         renderer = self.nrwrapper.front_renderer
         layer = self.nrwrapper.static_layer(renderer, self.ground_xz)
-        temp_f = np.asarray(temp_f)
-        smpl_f = np.asarray(smpl_handle.faces)
-        nvs = 6890
-        faces = np.concatenate([smpl_f, temp_f + nvs], 0).astype(np.int32)
-        colors = np.concatenate([np.tile(np.asarray(self.nrwrapper.colors[0], np.float32), (len(smpl_f), 1)),
-                                 np.tile(np.asarray(self.nrwrapper.colors[1], np.float32), (len(temp_f), 1))], 0)
-        tv = torch.as_tensor(np.asarray(temp_v), dtype=torch.float32, device=dev)
-        nv_mesh = nvs + tv.shape[0]
-        cviz = self.nrwrapper.contacts() if viz_contact else None
-        spheres = viz_contact and self.nrwrapper.contact_viz_type == 'sphere'
-        if spheres:
-            sf, sc = cviz.sphere_faces_colors(nv_mesh)
-            faces, colors = np.concatenate([faces, sf], 0), np.concatenate([colors, sc], 0)
-        faces_d = torch.as_tensor(faces, device=dev); colors_d = torch.as_tensor(colors, device=dev)
+        sc = self._scene(temp_v, temp_f, smpl_handle, viz_contact)
+        faces_d, colors_d, nv_mesh = sc.faces_d, sc.colors_d, sc.nv_mesh
+        first = 1 + (n if overlay else 0)                                   # panel index of camera kid's first render
         if add_top:
             top_layer = self.nrwrapper.static_layer(renderer, self.ground_xy)
             Ht, Wt, _ = self.top_shape(n)
@@ -685,21 +776,7 @@ class RendererSide2side:
                 idx = frames[c0:c0 + chunk]
                 nc = len(idx)
                 images = next(sources) if sources is not None else None          # with a pool, the next chunk's are being decoded from here on
-                ii = torch.as_tensor(idx, device=dev)
-                per_recon, per_colors = [], []
-                for d in recons:
-                    g = lambda k, w: torch.as_tensor(np.asarray(d[k], np.float32).reshape(T, w), device=dev)[ii].contiguous()
-                    sv, _, _ = ops.smplh_forward(smpl_handle, g("poses", 156), g("betas", 10), g("trans", 3))
-                    R = g("obj_angles", 9).reshape(nc, 3, 3); t = g("obj_trans", 3); s = g("obj_scales", 1)
-                    ov = (tv[None] @ R + t[:, None]) * s[:, :, None]
-                    block = [sv.detach(), ov]
-                    if viz_contact:
-                        reg = cviz.regions(block[0], ov)
-                        if spheres:
-                            block.append(cviz.spheres(reg))
-                        else:
-                            per_colors.append(cviz.face_colors(reg["part"], temp_f, len(smpl_f), colors_d))
-                    per_recon.append(torch.cat(block, 1))
+                per_recon, per_colors = self._chunk_meshes(sc, recons, smpl_handle, idx)
                 views = torch.stack([torch.stack([kin.world2local_torch(v, k) for v in per_recon], 1) for k in kids], 1)   # (nc, 2, n, NV, 3)
                 views = views.reshape(nc * 2 * n, views.shape[-2], 3).contiguous()
                 if bool((views[:, :nv_mesh, 2].amin() < 0).item()):
@@ -711,7 +788,7 @@ class RendererSide2side:
                 out = self.nrwrapper.raster.render(views, faces_d, cols, renderer, static=layer)
                 buf = torch.zeros(nc, H, W, 3, dtype=torch.uint8, device=dev)
                 b = torch.arange(nc * 2 * n, device=dev)
-                off = (b // (2 * n)) * (H * W * 3) + (1 + b % (2 * n)) * (pw * 3)
+                off = (b // (2 * n)) * (H * W * 3) + (first + b % (2 * n)) * (pw * 3)
                 panels_u8(out["rgb"], buf, off, 0, H, cs, pw, W * 3)
                 if images is not None:
                     device_panels(images, buf, size, cs, ce)
@@ -720,6 +797,11 @@ class RendererSide2side:
                         img = rgb(i) if callable(rgb) else rgb[i]
                         img = resize_bilinear_hw(np.asarray(img), H, size)[:, cs:ce]
                         buf[j, :, :pw] = torch.as_tensor(np.ascontiguousarray(img), device=dev)
+                if overlay:                                                          # behind the camera panel, on the same stream
+                    fit = self.fit_views(sc, per_recon, per_colors, kin)
+                    b = torch.arange(nc * n, device=dev)
+                    src = (b // n) * (H * W * 3)
+                    ops.overlay_panel_u8(fit["rgb"], fit["alpha"], buf, src, src + (1 + b % n) * (pw * 3), 0, H, cs, pw, W * 3, float(overlay_opacity))
                 if not add_top:
                     yield buf if on_device else buf.cpu().numpy()
                     continue
