@@ -639,6 +639,29 @@ int vt_overlay_panel_u8(const float *rgb, const float *alpha, int B, int size, i
 int vt_mask_score(const int *fidx, int B, int is, int rows, int F, int nf_body, int nf_obj, const unsigned char *pm, long long pm_bytes, const unsigned char *om,
                   long long om_bytes, const long long *frames, int thres, int *count, void *stream);
 
+/* ---- labels of SIF-Net's training samples: exact point-to-mesh distance and nearest vertex (preprocess/boundary_sampler.py:75-100 compute_labels:
+ * igl.signed_distance -> |distance| and closest surface point per mesh, trimesh.proximity.ProximityQuery.vertex -> nearest SMPL vertex) ---------------------
+ * PARITY UNPINNED, RESTATED FROM THE GEOMETRIC DEFINITION: igl, trimesh and psbody are not installed, so nothing is recorded from them; the pin is the float64
+ * brute force of tests/pmdist_model.py.  The arithmetic contract (closest point of a triangle by Voronoi region in fp32, the triangles as near as the minimum
+ * within fp32 rounding re-evaluated in fp64 to decide the winner, zero-area triangles as their longest edge, bounding-sphere culling that changes no result) is
+ * written in pmdist.hip's header, with the coordinate range the fp64 decision is guaranteed for (corners not much farther out than ~10 |p|_1).  INPUTS ARE FINITE BY CONTRACT: a NaN or infinite coordinate gives
+ * unspecified (but in-bounds) results.  Results do not depend on B or on a frame's place in the batch; no float atomics.
+ *
+ * vt_point_mesh_distance (boundary_sampler.py:75-100): points (B,N,3), verts (B,NV,3) one mesh pose per frame, faces (NF,3) int32 shared by the frames, every
+ *   index in [0,NV) (indices outside are clamped into it, for memory safety only) -> dist (B,N) unsigned distance = |p - closest| of the fp32 point written
+ *   to closest (B,N,3; may be NULL); face_id (B,N; may be NULL) int32 = the smallest index among the faces attaining the (fp64-arbitrated) minimum.  workspace:
+ *   vt_point_mesh_workspace_bytes(B, NF) bytes (-1 on bad sizes), 16-byte aligned, overwritten by every call.  B <= 65535.
+ * vt_point_mesh_distance_ex: the same with flags (bit 0: culling off, every triangle is evaluated; results are bit-identical either way) and n_tests (one
+ *   device-side 64-bit word, or NULL): the call ADDS the number of point-triangle evaluations it executed (the caller zeroes it).  Measurement and tests.
+ * vt_nearest_vertex (boundary_sampler.py:87,97 ProximityQuery.vertex): vert_id (B,N) int32 = argmin_j |p - v_j|^2 on the squared fp32 distance
+ *   ((dx dx + dy dy) + dz dz), exact ties to the smaller index; vert_dist (B,N; may be NULL) its sqrtf. */
+long vt_point_mesh_workspace_bytes(int B, int n_faces);
+int vt_point_mesh_distance(const float *points, int n_points, const float *verts, int n_verts, const int *faces, int n_faces, int B, float *dist, float *closest,
+                           int *face_id, void *workspace, void *stream);
+int vt_point_mesh_distance_ex(const float *points, int n_points, const float *verts, int n_verts, const int *faces, int n_faces, int B, float *dist,
+                              float *closest, int *face_id, void *workspace, int flags, unsigned long long *n_tests, void *stream);
+int vt_nearest_vertex(const float *points, int n_points, const float *verts, int n_verts, int B, int *vert_id, float *vert_dist, void *stream);
+
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two
  * workgroups of 256 threads per CU, non-trivial operands), out[1] = shader clock sustained during it (MHz: s_memtime against the 100 MHz s_memrealtime),

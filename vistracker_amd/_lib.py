@@ -145,6 +145,10 @@ SIGNATURES = {
     "vt_resize_panel_u8": (ci, [fp, C.c_longlong, vp, ci, ci, ci, ci, ci, fp, fp, C.c_longlong, vp]),
     "vt_overlay_panel_u8": (ci, [fp, fp, ci, ci, ci, ci, ci, ci, fp, fp, fp, C.c_longlong, cf, vp]),
     "vt_mask_score": (ci, [fp, ci, ci, ci, ci, ci, ci, fp, C.c_longlong, fp, C.c_longlong, vp, ci, fp, vp]),
+    "vt_point_mesh_workspace_bytes": (cl, [ci, ci]),
+    "vt_point_mesh_distance": (ci, [fp, ci, fp, ci, fp, ci, ci, fp, fp, fp, vp, vp]),
+    "vt_point_mesh_distance_ex": (ci, [fp, ci, fp, ci, fp, ci, ci, fp, fp, fp, vp, ci, fp, vp]),
+    "vt_nearest_vertex": (ci, [fp, ci, fp, ci, ci, fp, fp, vp]),
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
 }

@@ -475,6 +475,83 @@ def collision_loss(smpl_verts, smpl_faces, obj_verts, obj_faces, sigma=0.5, max_
 
 
 # --------------------------------------------------------------------------------------------------
+# exact point-to-mesh distance / nearest vertex (csrc/pmdist.hip; PARITY UNPINNED: igl, trimesh)
+# --------------------------------------------------------------------------------------------------
+def _frames(t, name):
+    """(B,K,3) float32 contiguous view of a (K,3) or (B,K,3) tensor, and whether a frame axis was added"""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise L.VtError(f"{name}: a device tensor expected; there is no CPU path")
+    t = _f32(t)
+    single = t.dim() == 2
+    if single:
+        t = t[None]
+    if t.dim() != 3 or t.shape[-1] != 3 or t.shape[1] == 0:
+        raise L.VtError(f"{name}: (B,K,3) or (K,3) with K > 0 expected, got {tuple(t.shape)}")
+    return t.contiguous(), single
+
+
+def check_faces(faces, n_verts):
+    """(NF,3) int32 contiguous device tensor of ``faces``; raises unless every index is in [0, n_verts).  Reads two scalars back from the device: callers
+    that reuse a mesh (BoundarySampler) call it once and pass ``validate=False`` to point_mesh_distance afterwards."""
+    f = torch.as_tensor(faces)
+    if f.dim() != 2 or f.shape[1] != 3 or f.shape[0] == 0 or f.dtype.is_floating_point:
+        raise L.VtError(f"faces: (NF,3) integers with NF > 0 expected, got {tuple(f.shape)} {f.dtype}")
+    lo, hi = int(f.min()), int(f.max())
+    if lo < 0 or hi >= n_verts:
+        raise L.VtError(f"faces: vertex indices span [{lo}, {hi}] but the mesh has {n_verts} vertices")
+    return f.to(torch.int32).contiguous()
+
+
+def point_mesh_distance(points, verts, faces, want_closest=True, want_face=True, validate=True, culling=True, n_tests=None):
+    """vt_point_mesh_distance (igl.signed_distance's |distance| and closest point, boundary_sampler.py:75-100): points (B,N,3), verts (B,NV,3) one mesh
+    pose per frame, faces (NF,3) shared -> (dist (B,N), closest (B,N,3), face_id (B,N) int32) device tensors; a single frame may come as (N,3) / (NV,3)
+    and is answered without the frame axis.  ``want_closest`` / ``want_face`` False returns None in that place (the kernel then skips the stores).
+    ``culling`` False and ``n_tests`` (a zeroed (1,) int64 device tensor the call adds its executed point-triangle tests to) go through
+    vt_point_mesh_distance_ex: measurement and tests only, the results are bit-identical."""
+    p, single = _frames(points, "points")
+    v, vsingle = _frames(verts, "verts")
+    if single != vsingle or p.shape[0] != v.shape[0] or p.device != v.device:
+        raise L.VtError(f"point_mesh_distance: points {tuple(p.shape)} and verts {tuple(v.shape)} must share the frame axis and the device")
+    B, N = p.shape[:2]; NV = v.shape[1]
+    f = check_faces(faces, NV) if validate else faces
+    if f.dtype != torch.int32 or f.device != p.device:
+        f = f.to(device=p.device, dtype=torch.int32)
+    f = f.contiguous(); NF = f.shape[0]
+    dev = p.device
+    with torch.cuda.device(dev):
+        ws = torch.empty((L.lib().vt_point_mesh_workspace_bytes(B, NF) + 15) // 16, 2, dtype=torch.int64, device=dev)
+        dist = torch.empty(B, N, device=dev)
+        closest = torch.empty(B, N, 3, device=dev) if want_closest else None
+        face_id = torch.empty(B, N, dtype=torch.int32, device=dev) if want_face else None
+        if culling and n_tests is None:
+            L.check(L.lib().vt_point_mesh_distance(L.dptr(p), N, L.dptr(v), NV, L.dptr(f), NF, B, L.dptr(dist), L.dptr(closest), L.dptr(face_id), L.dptr(ws),
+                                                   L.stream_ptr()))
+        else:
+            if n_tests is not None and (n_tests.dtype != torch.int64 or n_tests.numel() != 1):
+                raise L.VtError("point_mesh_distance: n_tests is a (1,) int64 device tensor")
+            L.check(L.lib().vt_point_mesh_distance_ex(L.dptr(p), N, L.dptr(v), NV, L.dptr(f), NF, B, L.dptr(dist), L.dptr(closest), L.dptr(face_id), L.dptr(ws),
+                                                      0 if culling else 1, L.dptr(n_tests), L.stream_ptr()))
+    if single:
+        dist, closest, face_id = dist[0], (closest[0] if want_closest else None), (face_id[0] if want_face else None)
+    return dist, closest, face_id
+
+
+def nearest_vertex(points, verts, want_dist=True):
+    """vt_nearest_vertex (trimesh.proximity.ProximityQuery.vertex, boundary_sampler.py:87,97): points (B,N,3), verts (B,NV,3) -> (vert_id (B,N) int32,
+    vert_dist (B,N) or None); exact ties go to the smaller index.  (N,3) / (NV,3) for a single frame."""
+    p, single = _frames(points, "points")
+    v, vsingle = _frames(verts, "verts")
+    if single != vsingle or p.shape[0] != v.shape[0] or p.device != v.device:
+        raise L.VtError(f"nearest_vertex: points {tuple(p.shape)} and verts {tuple(v.shape)} must share the frame axis and the device")
+    B, N = p.shape[:2]; dev = p.device
+    with torch.cuda.device(dev):
+        vid = torch.empty(B, N, dtype=torch.int32, device=dev)
+        vd = torch.empty(B, N, device=dev) if want_dist else None
+        L.check(L.lib().vt_nearest_vertex(L.dptr(p), N, L.dptr(v), v.shape[1], B, L.dptr(vid), L.dptr(vd), L.stream_ptr()))
+    return (vid[0], vd[0] if want_dist else None) if single else (vid, vd)
+
+
+# --------------------------------------------------------------------------------------------------
 # silhouette
 # --------------------------------------------------------------------------------------------------
 class _SilFn(torch.autograd.Function):
