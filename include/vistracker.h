@@ -662,6 +662,24 @@ int vt_point_mesh_distance_ex(const float *points, int n_points, const float *ve
                               float *closest, int *face_id, void *workspace, int flags, unsigned long long *n_tests, void *stream);
 int vt_nearest_vertex(const float *points, int n_points, const float *verts, int n_verts, int B, int *vert_id, float *vert_dist, void *stream);
 
+/* ---- SIF-Net's training objective at labelled points (model/chore_tri_vis.py:52-99 CHORETriplaneVisibility.get_errors, model/chore.py:312-325 get_df_loss;
+ * called by every training step and validation pass: trainer/trainer.py:108-150,321-346).  losshead.hip's header holds the arithmetic contract, the float64
+ * model tests/losshead_model.py restates it, tests/golden/losshead.npz records the reference's own values and autograd gradients.
+ *
+ * vt_sifnet_loss_head: predictions of S >= 1 stacks in the reference layout with a leading stack axis: df (S,B,2,N), pca (S,B,9,N), parts (S,B,14,N), centers
+ *   (S,B,3,N), vis (S,B,1,N).  Labels: df_h, df_o (B,N); parts_gt (B,N) int32 (a value outside [0,14) is clamped, for definedness only); pca_gt, obj_center,
+ *   visibility per point ((B,9,N), (B,3,N), (B,N); per_frame = 0) or per frame ((B,9), (B,3), (B); per_frame = 1), with identical bits.  weights: six HOST doubles
+ *   in the order of loss_weights (dfh, dfo, parts, pca, obj_center, vis); vis_loss 0 = l1, 1 = l2.  terms: six device doubles, the entries of the reference's
+ *   losses_all in ITS slot order (df_h, df_o, parts, pca, vis, obj_center), averaged over the stacks and UNWEIGHTED; error = terms[0] w0 + terms[1] w1 + terms[2] w2
+ *   + terms[3] w3 + terms[4] w5 + terms[5] w4.  d_df .. d_vis: gradients of gscale * error in the layouts of the predictions, overwritten; each may be NULL.
+ *   workspace: vt_sifnet_loss_head_ws_bytes(B, N) bytes (-1 on bad sizes), 8-byte aligned.  Two launches on the stream, no atomics: the same inputs give the same
+ *   bits on every call, with or without gradient pointers.  B <= 65535. */
+long vt_sifnet_loss_head_ws_bytes(int B, int n_points);
+int vt_sifnet_loss_head(const float *df, const float *pca, const float *parts, const float *centers, const float *vis, int S, int B, int n_points,
+                        const float *df_h, const float *df_o, const int *parts_gt, const float *pca_gt, const float *obj_center, const float *visibility,
+                        int per_frame, float max_dist, const double *weights, int vis_loss, float gscale, double *terms, float *d_df, float *d_pca,
+                        float *d_parts, float *d_centers, float *d_vis, void *workspace, void *stream);
+
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two
  * workgroups of 256 threads per CU, non-trivial operands), out[1] = shader clock sustained during it (MHz: s_memtime against the 100 MHz s_memrealtime),

@@ -149,6 +149,8 @@ SIGNATURES = {
     "vt_point_mesh_distance": (ci, [fp, ci, fp, ci, fp, ci, ci, fp, fp, fp, vp, vp]),
     "vt_point_mesh_distance_ex": (ci, [fp, ci, fp, ci, fp, ci, ci, fp, fp, fp, vp, ci, fp, vp]),
     "vt_nearest_vertex": (ci, [fp, ci, fp, ci, ci, fp, fp, vp]),
+    "vt_sifnet_loss_head_ws_bytes": (cl, [ci, ci]),
+    "vt_sifnet_loss_head": (ci, [fp, fp, fp, fp, fp, ci, ci, ci, fp, fp, fp, fp, fp, fp, ci, cf, C.POINTER(cd), ci, cf, fp, fp, fp, fp, fp, fp, vp, vp]),
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
 }

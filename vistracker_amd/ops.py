@@ -552,6 +552,133 @@ def nearest_vertex(points, verts, want_dist=True):
 
 
 # --------------------------------------------------------------------------------------------------
+# SIF-Net's training objective at labelled points (csrc/losshead.hip)
+# --------------------------------------------------------------------------------------------------
+LOSS_WEIGHTS = (1.0, 1.0, 0.006, 500.0, 1000.0, 1000.0)        # dfh, dfo, parts, pca, obj_center, vis (chore.py:86, config/tri-vis-l2.json:75)
+LOSS_SLOTS = ("df_h", "df_o", "parts", "pca", "vis", "obj_center")      # the reference's losses_all; the vis term sits in its loss_smpl_center slot
+LOSS_SLOT_WEIGHT = (0, 1, 2, 3, 5, 4)                          # slot -> index into loss_weights (chore_tri_vis.py:66-85)
+VIS_LOSSES = {"l1": 0, "l2": 1}
+_LOSS_WK = {}
+
+
+def _loss_dev(t, name):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise L.VtError(f"sifnet_loss_head: {name} must be a device tensor; there is no CPU path")
+    return t
+
+
+def _loss_preds(preds):
+    """five stacked (S,B,C,N) float32 contiguous tensors from five stacked tensors ((S,B,C,N), or (B,C,N) for one stack) or from a list of S five-tuples;
+    pca may come as (.., 3, 3, N).  One stack is a view; several tuples are stacked (a copy autograd sees through)."""
+    if len(preds) == 0:
+        raise L.VtError("sifnet_loss_head: no predictions")
+    if not torch.is_tensor(preds[0]):
+        stacks = [tuple(p) for p in preds]
+        if any(len(p) != 5 for p in stacks):
+            raise L.VtError("sifnet_loss_head: every stack is a (df, pca, parts, centers, vis) tuple")
+        for p in stacks:
+            for t, name in zip(p, HEADS):
+                _loss_dev(t, name)
+        B, N = stacks[0][0].shape[0], stacks[0][0].shape[-1]
+        heads = [torch.stack([p[i].reshape(B, k, N) for p in stacks]) if len(stacks) > 1 else stacks[0][i].reshape(1, B, k, N) for i, k in enumerate(HEAD_DIMS)]
+    else:
+        if len(preds) != 5:
+            raise L.VtError("sifnet_loss_head: five prediction tensors (df, pca, parts, centers, vis) expected")
+        for t, name in zip(preds, HEADS):
+            _loss_dev(t, name)
+        N = preds[0].shape[-1]
+        if preds[0].dim() not in (3, 4):
+            raise L.VtError(f"sifnet_loss_head: df is (S,B,2,N) or (B,2,N), got {tuple(preds[0].shape)}")
+        S, B = (1, preds[0].shape[0]) if preds[0].dim() == 3 else tuple(preds[0].shape[:2])
+        heads = [t.reshape(S, B, k, N) for t, k in zip(preds, HEAD_DIMS)]
+    S, B, _, N = heads[0].shape
+    if B == 0 or N == 0:
+        raise L.VtError(f"sifnet_loss_head: B = {B}, N = {N}")
+    for t, k, name in zip(heads, HEAD_DIMS, HEADS):
+        if tuple(t.shape) != (S, B, k, N) or t.dtype != torch.float32:
+            raise L.VtError(f"sifnet_loss_head: {name} is float32 ({S},{B},{k},{N}), got {t.dtype} {tuple(t.shape)}")
+    return [t.contiguous() for t in heads]
+
+
+class _LossHeadFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, df, pca, parts, centers, vis, labels, per_frame, max_dist, weights, vis_loss):
+        heads = (df, pca, parts, centers, vis)
+        S, B, _, N = df.shape
+        dev = df.device
+        want = any(ctx.needs_input_grad[:5])
+        with torch.cuda.device(dev):
+            grads = [torch.empty_like(t) if want and ctx.needs_input_grad[i] else None for i, t in enumerate(heads)]
+            terms = torch.empty(6, dtype=torch.float64, device=dev)
+            ws = torch.empty(L.lib().vt_sifnet_loss_head_ws_bytes(B, N) // 8, dtype=torch.float64, device=dev)
+            w = (C.c_double * 6)(*weights)
+            L.check(L.lib().vt_sifnet_loss_head(*[L.dptr(t) for t in heads], S, B, N, *[L.dptr(t) for t in labels], int(per_frame), float(max_dist), w,
+                                                int(vis_loss), 1.0, L.dptr(terms), *[L.dptr(g) for g in grads], L.dptr(ws), L.stream_ptr()))
+        ctx.grads = grads
+        key = (dev.index, weights)
+        if key not in _LOSS_WK:                                # the slot weights on the device, uploaded once per (device, weights)
+            if len(_LOSS_WK) > 16:
+                _LOSS_WK.clear()
+            _LOSS_WK[key] = torch.tensor([float(weights[i]) for i in LOSS_SLOT_WEIGHT], dtype=torch.float64, device=dev)
+        wk = _LOSS_WK[key]
+        losses_all = terms * wk
+        ctx.mark_non_differentiable(terms, losses_all)
+        return losses_all.sum(), losses_all, terms
+
+    @staticmethod
+    def backward(ctx, g, _gl, _gt):
+        g = g.to(torch.float32)
+        return tuple(None if d is None else d * g for d in ctx.grads) + (None,) * 5
+
+
+def sifnet_loss_head(preds, df_h, df_o, parts_gt, pca_gt, obj_center, visibility, max_dist=5.0, weights=LOSS_WEIGHTS, vis_loss="l2", validate=False,
+                     want_terms=False):
+    """vt_sifnet_loss_head: the six losses of CHORETriplaneVisibility.get_errors (chore_tri_vis.py:52-99) and, through autograd, their gradient to the
+    predictions.  ``preds``: a list of S (df (B,2,N), pca (B,9,N) or (B,3,3,N), parts (B,14,N), centers (B,3,N), vis (B,1,N)) tuples -- one per hourglass stack,
+    ``SIFNetQuery.intermediate_preds_list`` -- or the five tensors already stacked to (S,B,C,N).  Labels: df_h, df_o (B,N); parts_gt (B,N) integers (or floats
+    holding integers, as the reference's loader delivers them); pca_gt (B,9,N) / (B,3,3,N), obj_center (B,3,N), visibility (B,N) per point, or (B,9) / (B,3,3),
+    (B,3), (B) per frame (the compact form: the same bits); mixed forms are expanded to per point.  Device tensors only.  ``validate`` checks that every part
+    label is in [0,14) -- it reads the device, so it is off by default; the kernel clamps.
+    -> (error, losses_all): float64 device tensors, () and (6,); losses_all is weighted and in the reference's slot order (LOSS_SLOTS); with ``want_terms`` also
+    the unweighted terms.  The gradients are computed by the same launch as the values, and only for the predictions that require grad."""
+    heads = _loss_preds(preds)
+    S, B, _, N = heads[0].shape
+    dev = heads[0].device
+    if vis_loss not in VIS_LOSSES:
+        raise L.VtError(f"sifnet_loss_head: unknown vis_loss {vis_loss!r} (l1 or l2)")
+    if len(weights) != 6:
+        raise L.VtError("sifnet_loss_head: six loss weights expected")
+    for t, name in ((df_h, "df_h"), (df_o, "df_o"), (parts_gt, "parts_gt"), (pca_gt, "pca_gt"), (obj_center, "obj_center"), (visibility, "visibility")):
+        if _loss_dev(t, name).device != dev:
+            raise L.VtError(f"sifnet_loss_head: {name} on {t.device}, the predictions on {dev}")
+    if tuple(df_h.shape) != (B, N) or tuple(df_o.shape) != (B, N) or tuple(parts_gt.shape) != (B, N):
+        raise L.VtError(f"sifnet_loss_head: df_h, df_o, parts_gt are ({B},{N}), got {tuple(df_h.shape)}, {tuple(df_o.shape)}, {tuple(parts_gt.shape)}")
+    if validate:
+        lo, hi = float(parts_gt.min()), float(parts_gt.max())
+        if lo < 0 or hi > HEAD_DIMS[2] - 1:
+            raise L.VtError(f"sifnet_loss_head: part labels span [{lo:g}, {hi:g}], outside [0, {HEAD_DIMS[2]})")
+    frame = {"pca_gt": (pca_gt, 9), "obj_center": (obj_center, 3), "visibility": (visibility, 1)}
+    kinds = {}
+    for name, (t, k) in frame.items():
+        if t.numel() == B * k * N and (N > 1 or t.dim() > (1 if k == 1 else 2)):
+            kinds[name] = False
+        elif t.numel() == B * k:
+            kinds[name] = True
+        else:
+            raise L.VtError(f"sifnet_loss_head: {name} holds {B} x {k} x {N} values per point or {B} x {k} per frame, got {tuple(t.shape)}")
+    per_frame = all(kinds.values())
+    lab = []
+    for name, (t, k) in frame.items():
+        t = _f32(t)
+        if kinds[name] and not per_frame:
+            t = t.reshape(B, k, 1).expand(B, k, N)
+        lab.append(t.reshape(B, k) if per_frame else t.reshape(B, k, N).contiguous())
+    labels = (_f32(df_h), _f32(df_o), parts_gt.detach().to(torch.int32).contiguous(), *lab)
+    error, losses_all, terms = _LossHeadFn.apply(*heads, labels, per_frame, max_dist, tuple(float(w) for w in weights), VIS_LOSSES[vis_loss])
+    return (error, losses_all, terms) if want_terms else (error, losses_all)
+
+
+# --------------------------------------------------------------------------------------------------
 # silhouette
 # --------------------------------------------------------------------------------------------------
 class _SilFn(torch.autograd.Function):

@@ -28,6 +28,10 @@ class SIFNetQuery:
         self.device = device
         self.maps = None
         self.preds = None
+        self.intermediate_preds_list = []        # one prediction tuple per stack; the eval-mode query leaves one (chore.py:189-209)
+        self.loss_weights = list(ops.LOSS_WEIGHTS)       # dfh, dfo, parts, pca, obj_center, vis (chore.py:86)
+        self.vis_loss_name = "l2"                        # config/tri-vis-l2.json:74
+        self.error_buffer = None
         self.training = False
         self.encoder = None         # vistracker_amd.encoder.SIFNetEncoder (set by from_state_dict when the checkpoint holds encoder weights)
 
@@ -76,6 +80,24 @@ class SIFNetQuery:
         df, pca, parts, centers, vis = ops.sifnet_query(self.handle, self.maps, points, crop_center, body_center, 31)
         B, _, N = df.shape
         self.preds = (df, pca.view(B, 3, 3, N), parts, centers, vis)
+        self.intermediate_preds_list = [self.preds]
 
     def get_preds(self):
         return self.preds
+
+    def get_errors(self, df_h, df_o, parts_gt, pca_gt, max_dist, body_center, obj_center, **kwargs):
+        """CHORETriplaneVisibility.get_errors (chore_tri_vis.py:52-99) on ``self.intermediate_preds_list`` with the fused loss head
+        (``ops.sifnet_loss_head``): -> (error, losses_all), float64 device tensors; losses_all = the six weighted losses in the reference's slot order
+        (df_h, df_o, parts, pca, vis, obj_center), also kept in ``self.error_buffer``.  ``visibility`` comes as a keyword, as in the reference;
+        ``body_center`` is not used there either.  ``pca_gt`` (B,3,3,N), ``obj_center`` (B,3,N), ``visibility`` (B,N), or their per-frame forms (B,3,3),
+        (B,3), (B); ``parts_gt`` may be float.  ``validate_labels=True`` checks the part labels (one read of the device).  Nothing is printed: the reference's
+        print_errors would synchronise every step.  ``error.backward()`` reaches the query points through ``ops.sifnet_query``."""
+        vis_gt = kwargs.get("visibility")
+        if vis_gt is None:
+            raise ValueError("get_errors: the visibility labels come as the keyword `visibility`")
+        if not self.intermediate_preds_list:
+            raise RuntimeError("get_errors: call query() first")
+        error, losses_all = ops.sifnet_loss_head(self.intermediate_preds_list, df_h, df_o, parts_gt, pca_gt, obj_center, vis_gt, max_dist=max_dist,
+                                                 weights=self.loss_weights, vis_loss=self.vis_loss_name, validate=bool(kwargs.get("validate_labels", False)))
+        self.error_buffer = losses_all
+        return error, losses_all
