@@ -30,6 +30,7 @@ def hip(synth):
     assert torch.cuda.is_available(), "GPU tests need the MI355X box"
     return {
         "ops": ops,
+        "model": synth["model"],
         "smpl": ops.SmplhHandle(synth["model"]),
         "b25": ops.LandmarkHandle(synth["regs"]["body25"]),
         "face": ops.LandmarkHandle(synth["regs"]["face"]),
@@ -52,7 +53,32 @@ def test_rodrigues(hip):
     g = golden("rodrigues"); ops = hip["ops"]
     assert np.abs(npy(ops.rodrigues(cu(g["aa"]))) - g["R"]).max() < 2e-6
     d = npy(ops.rodrigues_bwd(cu(g["aa"]), cu(g["gR"])))
+    # The whole-array assertion has always left out rows 0 (theta = 0) and 1 (|theta| = 3.7e-4).  The fixture gives no reason to: its daa of both rows is the
+    # shifted definition's value, which the float64 model and the float32 oracle reproduce to 5e-8 of the row
+    # (tests/test_host_smplh_model.py::test_model_rodrigues_vs_golden).  That assertion stays as it was; every row, these two included, is held per row below.
     assert rel(d[2:], g["daa"][2:]) < 1e-4
+    _rodrigues_per_row(g["aa"], g["gR"], d)
+
+
+def _rodrigues_per_row(aa, gR, d_kernel):
+    """every rotation on its own scale against the float64 model: within GATE x the float32 oracle's worst row (the rule of tests/test_gpu_smplh_perjoint.py)"""
+    import smplh_model as M
+    from oracle import oracle as O
+    ref = M.rodrigues_bwd_np(aa, gR)
+    n = len(ref)
+    e32 = M.per_row_err(O.rodrigues_bwd(aa, gR).reshape(1, -1), ref.reshape(1, -1), n).max()
+    err = M.per_row_err(d_kernel.reshape(1, -1), ref.reshape(1, -1), n)
+    print(f"rodrigues_bwd per row: kernel {err.max():.2e} (row {int(err.argmax())}), fp32 oracle {e32:.2e}, gate {M.GATE * e32:.2e}")
+    assert (err <= M.GATE * e32).all(), (np.nonzero(err > M.GATE * e32)[0].tolist(), err.max(), M.GATE * e32)
+
+
+def test_rodrigues_backward_at_the_edge_angles(hip):
+    """vt_rodrigues_backward at 0, 1e-6, 0.3, pi - 1e-3 and 4.0 rad about a fixed axis (0 and 1e-6: where the 1e-8 shift of the norm matters; pi - 1e-3: the
+    quaternion's w ~ 0; 4.0: beyond pi), plus (1e-6, 1e-6, 1e-6), the row of the pose-edge case"""
+    axis = np.array([2.0, -1.0, 2.0]) / 3
+    aa = np.stack([axis * a for a in (0.0, 1e-6, 0.3, np.pi - 1e-3, 4.0)] + [np.full(3, 1e-6)]).astype(np.float32)
+    gR = np.random.default_rng(5).normal(0, 1, (len(aa), 9)).astype(np.float32)
+    _rodrigues_per_row(aa, gR, npy(hip["ops"].rodrigues_bwd(cu(aa), cu(gR))))
 
 
 def test_smplh_vs_golden(hip):
@@ -67,6 +93,16 @@ def test_smplh_vs_golden(hip):
     assert rel(npy(pose.grad), g["dpose"]) < 3e-4
     assert rel(npy(betas.grad), g["dbetas"]) < 3e-4
     assert rel(npy(trans.grad), g["dtrans"]) < 3e-4
+    # per joint / column / axis against the same golden.  The golden is the reference's float32 autograd: its own per-row error e_ref against the float64 model
+    # of the same inputs sizes the gate -- GATE x e_ref for the kernel's distance from the truth (the rule of tests/test_gpu_smplh_perjoint.py) + 1 x e_ref for
+    # the golden's.
+    import smplh_model as M
+    gold = (g["dpose"], g["dbetas"], g["dtrans"])
+    ref = M.SmplhModel(hip["model"]).backward(g["pose"], g["betas"], g["trans"], npy(gv), g["gj"])
+    gate = (M.GATE + 1) * M.worst(M.grad_errs(gold, ref))
+    errs = M.grad_errs((npy(pose.grad), npy(betas.grad), npy(trans.grad)), gold)
+    print(f"smplh vs golden per row: kernel {M.worst(errs):.2e}, gate {gate:.2e}")
+    assert gate < 1e-4 and M.worst(errs) <= gate, {k: (int(e.argmax()), float(e.max())) for k, e in errs.items()}
 
 
 @pytest.mark.parametrize("B", [1, 13, 96])
@@ -84,6 +120,24 @@ def test_smplh_vs_oracle_ragged_batches(hip, synth, B):
     assert np.abs(npy(verts) - v_o).max() < 3e-5 and np.abs(npy(jtr) - j_o).max() < 3e-5
     (verts * cu(gv)).sum().backward()
     assert rel(npy(p.grad), dp_o) < 3e-4 and rel(npy(b_.grad), db_o) < 3e-4 and rel(npy(t.grad), dt_o) < 3e-4
+    # per joint / column / axis against the same oracle, every row with a gate of its own: (GATE + 1) x e32 -- GATE x for the kernel's distance from the
+    # float64 model, 1 x for the oracle's own -- where e32 is the larger of the oracle's error on THAT row and its worst error over the well-conditioned rows
+    # (those it gets to 1e-5, the float32 round-off class tests/test_host_smplh_model.py holds every case's e32 to).  A row the input conditions badly
+    # therefore loosens only itself: at B = 1 a row is ONE sum of 20 670 terms of both signs, and with default_rng(1) column 3 of dbetas cancels to a scale
+    # of 1.2e-3, where the oracle is 3.2e-4 away from the model; the other 64 rows stay at 9 x 1.8e-6.
+    import smplh_model as M
+    ref = M.SmplhModel(synth["model"]).backward(pose, betas, trans, gv)
+    e32 = M.grad_errs((dp_o, db_o, dt_o), ref)
+    shared = max(float(e[e <= 1e-5].max()) for e in e32.values())
+    errs = M.grad_errs((npy(p.grad), npy(b_.grad), npy(t.grad)), (dp_o, db_o, dt_o))
+    gates = {k: (M.GATE + 1) * np.maximum(e32[k], shared) for k in e32}
+    print(f"smplh vs oracle per row, B = {B}: kernel {M.worst(errs):.2e}, shared gate {(M.GATE + 1) * shared:.2e}, rows with a gate of their own "
+          f"{ {k: np.nonzero(e32[k] > shared)[0].tolist() for k in e32 if (e32[k] > shared).any()} }")
+    for k in errs:
+        print(f"  {k}: worst row {int((errs[k] / gates[k]).argmax())} at {float((errs[k] / gates[k]).max()):.2f} of its gate")
+    assert (M.GATE + 1) * shared < 1e-4                                  # far below the 1e-3 error the assertion is there to catch
+    for k in errs:
+        assert (errs[k] <= gates[k]).all(), (k, np.nonzero(errs[k] > gates[k])[0].tolist(), errs[k][errs[k] > gates[k]], gates[k][errs[k] > gates[k]])
 
 
 def test_smplh_dense_weights_take_the_dense_lbs(hip, synth):
