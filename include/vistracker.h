@@ -680,6 +680,35 @@ int vt_sifnet_loss_head(const float *df, const float *pca, const float *parts, c
                         int per_frame, float max_dist, const double *weights, int vis_loss, float gscale, double *terms, float *d_df, float *d_pca,
                         float *d_parts, float *d_centers, float *d_vis, void *workspace, void *stream);
 
+/* ---- training SIF-Net's five point decoders with the feature maps frozen (dectrain.hip): a forward from PLAIN device weights and the gradient of the objective
+ * to every weight and bias -- what loss.backward() leaves in the decoders of the reference's train step.  dectrain.hip's header holds the arithmetic contract
+ * (exact fp32 products, fp32 accumulation on the f32-input MFMA; chunk partials added in fp64 in a fixed order; no atomics), tests/dectrain_model.py restates
+ * it in float64, tests/golden/dectrain.npz records the reference's own predictions and autograd gradients.
+ *
+ * PARAMETERS: one flat fp32 device buffer of vt_decoder_param_floats() floats.  For head h in the head order above (df 2, pca 9, parts 14, centers 3, vis 1) and
+ *   layer l = 0..3 it holds W_hl (out,in) row-major (torch's Conv1d.weight[:, :, 0]) and then b_hl (out): the decoders of model/chore.py:113-126 make_decoder.
+ *   The `in` axis of layer 0 is the reference's 611-channel order (model/chore_triplane.py:139-151): im_feat 256, z_feat 3, tmpx 64, tri_tmpx 3 x 32, tri_feat
+ *   3 x 64.  vt_decoder_param_offset(head, layer, is_bias) is the offset (in floats) of W_hl or b_hl; -1 for a head or layer that does not exist.
+ * cam: HOST, the five floats of vt_sifnet_create.  maps: as vt_query_forward (its proj, act_level and force_fp32 fields are ignored).  B <= 65535.
+ *
+ * vt_decoder_train_forward (model/chore_triplane.py:97-164 query, model/geometry.py:4-14 index, model/chore.py:113-126): the projection, the eight bilinear
+ *   gathers (grid_sample, align_corners=True, zeros padding), z_feat and the five decoders from `params`.  Outputs as vt_query_forward (NULL skips a head);
+ *   df is OUT_DIST = 5.0 where the point projects outside the image (chore_triplane.py:155-159); vis carries its sigmoid.
+ * vt_decoder_weight_grads (trainer/trainer.py:97-106: the loss.backward() of train_step, decoder parameters only): d_df .. d_vis are the upstream gradients in
+ *   the prediction layouts; NULL = zero, and that head's slice of dparams is then exactly zero.  d_df of an out-of-image point counts as zero.  dparams has the
+ *   layout of params; overwritten when accumulate == 0, added to otherwise (S stacks of maps share one buffer).  Sums over points: fp32 on the MFMA over at most
+ *   chunk_points points of one frame (0 = the default, 2048; otherwise a multiple of 64 up to 16384), the chunk partials then in fp64 in the order (frame,
+ *   chunk) and rounded to fp32 once.  The same inputs give the same bits on every call.  workspace: vt_decoder_weight_grads_ws_bytes(B, N, chunk_points) bytes
+ *   (-1 on bad sizes), 16-byte aligned; nothing in it needs initialising, all of it is overwritten.  Nothing is computed for points or feature maps. */
+long vt_decoder_param_floats(void);
+long vt_decoder_param_offset(int head, int layer, int is_bias);
+int vt_decoder_train_forward(const float *params, const float *cam, const vt_maps *maps, const float *pts, const float *crop_center, const float *body_center,
+                             int B, int N, float *df, float *pca, float *parts, float *centers, float *vis, void *stream);
+long vt_decoder_weight_grads_ws_bytes(int B, int N, int chunk_points);
+int vt_decoder_weight_grads(const float *params, const float *cam, const vt_maps *maps, const float *pts, const float *crop_center, const float *body_center,
+                            int B, int N, const float *d_df, const float *d_pca, const float *d_parts, const float *d_centers, const float *d_vis,
+                            float *dparams, int accumulate, int chunk_points, void *workspace, void *stream);
+
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two
  * workgroups of 256 threads per CU, non-trivial operands), out[1] = shader clock sustained during it (MHz: s_memtime against the 100 MHz s_memrealtime),

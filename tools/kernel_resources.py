@@ -7,7 +7,8 @@ import subprocess
 import sys
 
 NO_SCRATCH = ("query_kernel<2, 2, true>", "query_kernel<2, 2, false>", "query_kernel<1, 3, true>", "query_kernel<1, 3, false>", "inp_panel_kernel", "ovl_panel_kernel",
-              "ovl_score_kernel<true>", "ovl_score_kernel<false>", "pm_dist_kernel", "pm_vertex_kernel", "pm_setup_kernel", "ll_loss_kernel", "ll_finish_kernel")
+              "ovl_score_kernel<true>", "ovl_score_kernel<false>", "pm_dist_kernel", "pm_vertex_kernel", "pm_setup_kernel", "ll_loss_kernel", "ll_finish_kernel",
+              "dect::feat_kernel", "dect::mlp_kernel<0>", "dect::mlp_kernel<1>", "dect::wgrad_kernel", "dect::finish_kernel")
 
 rows, cur = [], None
 for line in sys.stdin:

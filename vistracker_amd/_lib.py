@@ -151,6 +151,11 @@ SIGNATURES = {
     "vt_nearest_vertex": (ci, [fp, ci, fp, ci, ci, fp, fp, vp]),
     "vt_sifnet_loss_head_ws_bytes": (cl, [ci, ci]),
     "vt_sifnet_loss_head": (ci, [fp, fp, fp, fp, fp, ci, ci, ci, fp, fp, fp, fp, fp, fp, ci, cf, C.POINTER(cd), ci, cf, fp, fp, fp, fp, fp, fp, vp, vp]),
+    "vt_decoder_param_floats": (cl, []),
+    "vt_decoder_param_offset": (cl, [ci, ci, ci]),
+    "vt_decoder_train_forward": (ci, [fp, vp, C.POINTER(VtMaps), fp, fp, fp, ci, ci, fp, fp, fp, fp, fp, vp]),
+    "vt_decoder_weight_grads_ws_bytes": (cl, [ci, ci, ci]),
+    "vt_decoder_weight_grads": (ci, [fp, vp, C.POINTER(VtMaps), fp, fp, fp, ci, ci, fp, fp, fp, fp, fp, fp, ci, ci, vp, vp]),
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
 }

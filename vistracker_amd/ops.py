@@ -679,6 +679,147 @@ def sifnet_loss_head(preds, df_h, df_o, parts_gt, pca_gt, obj_center, visibility
 
 
 # --------------------------------------------------------------------------------------------------
+# training the point decoders, feature maps frozen (csrc/dectrain.hip)
+# --------------------------------------------------------------------------------------------------
+STATE_DICT_MODULES = {"df": "df", "pca": "pca_predictor", "parts": "part_predictor", "centers": "center_predictor", "vis": "visib_predictor"}
+STATE_DICT_LAYERS = (0, 2, 4, 6)                               # the Conv1d entries of make_decoder's Sequential (chore.py:113-126)
+
+
+class DecoderParams:
+    """The weights and biases of the five decoders as ONE flat float32 tensor (``flat``, the leaf that requires grad: one Adam launch a step) in the layout of
+    ``vt_decoder_param_offset``, plus the 40 named views into it: ``views[(head, layer, "weight" | "bias")]``, (out, in) and (out,).  The offsets come from
+    the library; nothing here restates the table.  A container: it lives on any device, the kernels take it on the GPU only."""
+
+    def __init__(self, flat, cam=DEFAULT_CAM):
+        lib = L.lib()
+        n = int(lib.vt_decoder_param_floats())
+        if not torch.is_tensor(flat) or flat.dtype != torch.float32 or tuple(flat.shape) != (n,):
+            raise L.VtError(f"DecoderParams: a float32 tensor of {n} values expected")
+        self.flat = flat.detach().contiguous().requires_grad_(True)
+        self.cam = _np32(cam)
+        self.views, data = {}, self.flat.detach()
+        for h, (name, k) in enumerate(zip(HEADS, HEAD_DIMS)):
+            for l in range(4):
+                shape = (k if l == 3 else 128, MAP_CHANNELS_TOTAL if l == 0 else 128)
+                ow, ob = int(lib.vt_decoder_param_offset(h, l, 0)), int(lib.vt_decoder_param_offset(h, l, 1))
+                self.views[(name, l, "weight")] = data[ow:ow + shape[0] * shape[1]].view(shape)
+                self.views[(name, l, "bias")] = data[ob:ob + shape[0]]
+        if sum(v.numel() for v in self.views.values()) != n:
+            raise L.VtError("DecoderParams: the library's offsets do not tile the parameter buffer")
+
+    @classmethod
+    def from_decoders(cls, decoders: dict, cam=DEFAULT_CAM, device="cuda:0"):
+        """from the host form ``SIFNetQuery.decoders_from_state_dict`` produces: name -> four (weight (out,in), bias (out,)) pairs"""
+        p = cls(torch.zeros(int(L.lib().vt_decoder_param_floats())), cam)
+        for name in HEADS:
+            if len(decoders[name]) != 4:
+                raise L.VtError(f"DecoderParams: {name} has {len(decoders[name])} layers, 4 expected")
+            for l, (w, b) in enumerate(decoders[name]):
+                for kind, a in (("weight", w), ("bias", b)):
+                    v = p.views[(name, l, kind)]
+                    a = torch.as_tensor(_np32(a))
+                    if tuple(a.shape) != tuple(v.shape):
+                        raise L.VtError(f"DecoderParams: {name} layer {l} {kind} is {tuple(v.shape)}, got {tuple(a.shape)}")
+                    v.copy_(a)
+        return cls(p.flat.detach().to(device), cam)
+
+    def to_decoders(self) -> dict:
+        """-> the host form (numpy), what ``SIFNetQuery`` and ``SifNetHandle`` take"""
+        host = DecoderParams(self.flat.detach().cpu(), self.cam)
+        return {name: [(host.views[(name, l, "weight")].numpy().copy(), host.views[(name, l, "bias")].numpy().copy()) for l in range(4)] for name in HEADS}
+
+    def state_dict(self, prefix: str = "") -> dict:
+        """the reference's keys and Conv1d shapes: ``df.0.weight`` (128, 611, 1), ``df.0.bias`` (128,), ... ``visib_predictor.6.bias`` (1,); copies"""
+        out = {}
+        for name in HEADS:
+            for l, i in enumerate(STATE_DICT_LAYERS):
+                out[f"{prefix}{STATE_DICT_MODULES[name]}.{i}.weight"] = self.views[(name, l, "weight")].clone().unsqueeze(-1)
+                out[f"{prefix}{STATE_DICT_MODULES[name]}.{i}.bias"] = self.views[(name, l, "bias")].clone()
+        return out
+
+    def load_state_dict(self, sd: dict):
+        """in place, from the reference's keys with or without the ``module.`` prefix (other keys, the encoder's, are ignored); a missing key raises"""
+        with torch.no_grad():
+            for name in HEADS:
+                for l, i in enumerate(STATE_DICT_LAYERS):
+                    for kind in ("weight", "bias"):
+                        key = f"{STATE_DICT_MODULES[name]}.{i}.{kind}"
+                        t = sd.get(key, sd.get("module." + key))
+                        if t is None:
+                            raise KeyError(key)
+                        v = self.views[(name, l, kind)]
+                        t = torch.as_tensor(t, dtype=torch.float32)
+                        if t.numel() != v.numel():
+                            raise L.VtError(f"DecoderParams.load_state_dict: {key} holds {v.numel()} values, got {tuple(t.shape)}")
+                        v.copy_(t.reshape(v.shape))
+        return self
+
+
+MAP_CHANNELS_TOTAL = sum(MAP_CHANNELS) + 3                     # 611: the eight maps and z_feat
+
+
+def _train_maps(maps):
+    maps = [maps] if isinstance(maps, FeatureMaps) else list(maps)
+    if not maps or not all(isinstance(m, FeatureMaps) for m in maps):
+        raise L.VtError("sifnet_query_train: maps is a FeatureMaps or a list of them, one per stack")
+    if any(t.requires_grad for m in maps for t in m.t):
+        raise L.VtError("sifnet_query_train: the feature maps are frozen here; a map that requires grad would silently get none")
+    return maps
+
+
+class _QueryTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flat, cam, maps, pts, cc, bc, chunk_points):
+        B, N = pts.shape[:2]
+        outs = []
+        with torch.cuda.device(flat.device):
+            for m in maps:
+                o = [torch.empty(B, k, N, device=flat.device) for k in HEAD_DIMS]
+                L.check(L.lib().vt_decoder_train_forward(L.dptr(flat), cam.ctypes.data, C.byref(m.c), L.dptr(pts), L.dptr(cc), L.dptr(bc), B, N,
+                                                         *[L.dptr(t) for t in o], L.stream_ptr()))
+                outs += o
+        ctx.cam, ctx.maps, ctx.chunk = cam, maps, chunk_points
+        ctx.set_materialize_grads(False)                       # a prediction the objective does not use arrives as None -> NULL: its head costs nothing
+        ctx.save_for_backward(flat, pts, cc, bc)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        flat, pts, cc, bc = ctx.saved_tensors
+        B, N = pts.shape[:2]
+        with torch.cuda.device(flat.device):
+            dflat = torch.empty_like(flat)
+            ws = torch.empty(int(L.lib().vt_decoder_weight_grads_ws_bytes(B, N, ctx.chunk)) // 4 + 4, device=flat.device)
+            for s, m in enumerate(ctx.maps):
+                g = [None if t is None else _f32(t) for t in gs[5 * s:5 * s + 5]]
+                L.check(L.lib().vt_decoder_weight_grads(L.dptr(flat), ctx.cam.ctypes.data, C.byref(m.c), L.dptr(pts), L.dptr(cc), L.dptr(bc), B, N,
+                                                        *[L.dptr(t) for t in g], L.dptr(dflat), 1 if s else 0, int(ctx.chunk), L.dptr(ws), L.stream_ptr()))
+        return dflat, None, None, None, None, None, None
+
+
+def sifnet_query_train(params: DecoderParams, maps, pts, crop_center, body_center, chunk_points=0):
+    """The query of a training step (chore_triplane.py:97-164 in train mode) from the plain weights of ``params``: ``maps`` is one ``FeatureMaps`` or a list of
+    S, one per hourglass stack (they share their tmpx tensors, chore_triplane.py:139-149).  -> a list of S (df (B,2,N), pca (B,3,3,N), parts (B,14,N), centers
+    (B,3,N), vis (B,1,N)) tuples, the shape of ``intermediate_preds_list``.  Backward: one vt_decoder_weight_grads call per stack into ONE flat gradient
+    (``params.flat.grad``).  Points and maps are data here: there is no gradient for them, and one that requires grad raises."""
+    maps = _train_maps(maps)
+    if not isinstance(params, DecoderParams):
+        raise L.VtError("sifnet_query_train: params is an ops.DecoderParams")
+    for t, name in ((pts, "points"), (crop_center, "crop_center"), (body_center, "body_center")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise L.VtError(f"sifnet_query_train: {name} must be a device tensor; there is no CPU path")
+    if pts.requires_grad:
+        raise L.VtError("sifnet_query_train: the points are data here (no gradient flows to them); detach them, or use sifnet_query for the gradient to the points")
+    pts, cc, bc = _f32(pts), _f32(crop_center), _f32(body_center)
+    B, N = pts.shape[:2]
+    if pts.dim() != 3 or pts.shape[2] != 3 or tuple(cc.shape) != (B, 2) or tuple(bc.shape) != (B, 3) or any(m.B != B for m in maps):
+        raise L.VtError(f"sifnet_query_train: points (B,N,3), crop_center (B,2), body_center (B,3), maps of B frames; got {tuple(pts.shape)}, {tuple(cc.shape)}, "
+                        f"{tuple(bc.shape)}, {[m.B for m in maps]}")
+    outs = _QueryTrainFn.apply(params.flat, params.cam, maps, pts, cc, bc, int(chunk_points))
+    return [(outs[5 * s], outs[5 * s + 1].view(B, 3, 3, N), outs[5 * s + 2], outs[5 * s + 3], outs[5 * s + 4]) for s in range(len(maps))]
+
+
+# --------------------------------------------------------------------------------------------------
 # silhouette
 # --------------------------------------------------------------------------------------------------
 class _SilFn(torch.autograd.Function):

@@ -82,6 +82,17 @@ class SIFNetQuery:
         self.preds = (df, pca.view(B, 3, 3, N), parts, centers, vis)
         self.intermediate_preds_list = [self.preds]
 
+    def query_train(self, params, points, crop_center=None, body_center=None, maps=None, **kwargs):
+        """The query of a training step from the plain weights of ``params`` (an ``ops.DecoderParams``; this network's packed handle is not used): sets
+        ``preds`` and ``intermediate_preds_list`` as the reference's train-mode query does (chore_triplane.py:137-163), one tuple per stack.  ``maps``: a
+        ``FeatureMaps`` or a list of S of them (default: the maps set on this network, one stack).  ``get_errors`` then works unchanged and
+        ``error.backward()`` fills ``params.flat.grad``; the points and the maps get no gradient."""
+        maps = self.maps if maps is None else maps
+        assert maps is not None, "call set_feature_maps() (or filter()) first, or pass maps"
+        self.points, self.crop_center = points, crop_center
+        self.intermediate_preds_list = ops.sifnet_query_train(params, maps, points, crop_center, body_center, **kwargs)
+        self.preds = self.intermediate_preds_list[-1]
+
     def get_preds(self):
         return self.preds
 

@@ -4,7 +4,10 @@
 ``validate`` is one batch of the reference's ``compute_val_loss`` (trainer/trainer.py:321-346: query, then ``get_errors``, no gradient) with no host labelling.
 
 Out of scope here: file and ``KinectTransform`` IO (the meshes arrive in camera-local coordinates), image loading (``SequenceLoader(device_prep=True)``
-builds the network inputs), ``smpl_vect`` (``load_neighbour_h``), the weight and feature-map gradients of the decoders and the optimiser loop.
+builds the network inputs), ``smpl_vect`` (``load_neighbour_h``), the feature-map and encoder gradients, learning-rate schedules, checkpoint directories.
+
+``DecoderTrainer`` is the reference's ``Trainer.train_step`` (trainer/trainer.py:97-106) for the decoder parameter group: the five point decoders of a checkpoint
+are fine-tuned on labelled batches with the encoder, and so the feature maps, frozen.
 """
 from __future__ import annotations
 
@@ -88,3 +91,40 @@ def validate(net, batch, crop_center, max_dist=5.0):
                                            visibility=batch["visibility"])
         out = torch.cat([losses_all, error.reshape(1)]).cpu().tolist()
     return dict(zip(ops.LOSS_SLOTS + ("total",), out))
+
+
+class DecoderTrainer:
+    """``Trainer.train_step`` (trainer/trainer.py:97-106) with ``optim.Adam(param_groups, lr=1e-3)`` (trainer.py:31-44) for the decoders of ``net`` (a
+    ``SIFNetQuery``): the parameters are copied from ``net.decoders`` into one flat device tensor (``ops.DecoderParams``) that ``ops.FusedAdam`` updates with one
+    launch a step; ``net`` itself serves the maps, the loss weights and ``get_errors``, its packed handle is left alone.  ``export()`` hands the trained decoders
+    back as a new ``SIFNetQuery``."""
+
+    def __init__(self, net, lr=1e-3, max_dist=5.0):
+        self.net, self.max_dist = net, float(max_dist)
+        self.params = ops.DecoderParams.from_decoders(net.decoders, cam=net.camera.as_cam5(), device=net.device)
+        self.optimizer = ops.FusedAdam([self.params.flat], lr=lr)
+
+    def train_step(self, batch, crop_center, maps=None):
+        """one step on a batch of ``make_training_batch``: zero_grad, query, get_errors, backward, Adam.  ``maps``: a ``FeatureMaps`` or a list of S, one per
+        stack (default: the maps set on ``net``).  -> (error (), losses_all (6,)): float64 device tensors of the step's objective BEFORE the update; nothing
+        here synchronises."""
+        self.optimizer.zero_grad()
+        self.net.query_train(self.params, batch["points"], crop_center=crop_center, body_center=batch["body_center"], maps=maps)
+        error, losses_all = self.net.get_errors(batch["df_h"], batch["df_o"], batch["labels"], batch["pca_axis"], self.max_dist, batch["body_center"],
+                                                batch["obj_center"], visibility=batch["visibility"])
+        error.backward()
+        self.optimizer.step()
+        return error.detach(), losses_all
+
+    def state_dict(self, prefix=""):
+        """the decoders under the reference's checkpoint keys (``df.0.weight`` (128, 611, 1), ...)"""
+        return self.params.state_dict(prefix)
+
+    def export(self):
+        """-> a new ``SIFNetQuery`` holding the trained decoders (packed by ``vt_sifnet_create`` as any checkpoint's), with this network's camera, encoder, maps
+        and loss settings: it goes straight into ``validate``, the fit loops and the generator.  Reads the parameters back to the host once."""
+        from .sifnet import SIFNetQuery
+        out = SIFNetQuery(self.params.to_decoders(), camera=self.net.camera, device=self.net.device)
+        out.maps, out.encoder = self.net.maps, self.net.encoder
+        out.loss_weights, out.vis_loss_name = list(self.net.loss_weights), self.net.vis_loss_name
+        return out
