@@ -379,7 +379,8 @@ int vt_collision_loss(const float *smpl_verts, int n_smpl_verts, const int *smpl
  * Ragged contact Chamfer.  Replaces pytorch3d.loss.chamfer_distance(Pointclouds, Pointclouds)[0]
  * (recon/recon_fit_trivis_full.py:454-457; pytorch3d defaults, see DESIGN.md "unpinned").
  * x (nx_total,3), y (ny_total,3), offx/offy (P+1) int32 device.  *term += value.
- * dx, dy (+=, may be NULL) receive gscale * gradient.
+ * dx, dy (+=, may be NULL) receive gscale * gradient.  Nearest neighbour: smallest index among equal distances.  No float atomics on the gradients, and the
+ * pairs' shares of the term are added in pair order (stream-ordered scratch of P doubles, hipMallocAsync): the same bits on every run, in all three forms.
  * ------------------------------------------------------------------------------------------------- */
 int vt_chamfer_ragged(const float *x, const int *offx, const float *y, const int *offy, int P, float gscale,
                       double *term, float *dx, float *dy, void *stream);

@@ -69,7 +69,7 @@ __device__ __forceinline__ void chamfer_dir(const float *__restrict__ a, int na,
 }
 
 __global__ __launch_bounds__(CH_BLK) void chamfer_kernel(const float *__restrict__ x, const int *__restrict__ offx, const float *__restrict__ y,
-                                                      const int *__restrict__ offy, int P, float gs, double *term, float *dx, float *dy, const int *skip)
+                                                      const int *__restrict__ offy, int P, float gs, double *part, float *dx, float *dy, const int *skip)
 {
     VT_SKIP_RETURN(skip);
     __shared__ float4 sB4[CH_CHUNK];
@@ -89,19 +89,38 @@ __global__ __launch_bounds__(CH_BLK) void chamfer_kernel(const float *__restrict
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0 && term) {
+    // the pair's share of the term goes to part[p]; chamfer_term_kernel adds the shares in pair order (P fp64 atomics on one address arrive in a different order on
+    // every run, and the last bits of the term varied with it: tests/test_gpu_chamfer.py::test_repeatable)
+    if (threadIdx.x == 0 && part) {
         double tot = 0;
         for (int w = 0; w < CH_BLK / 64; w++) tot += red[w];
-        atomicAdd(term, tot / (double)P);
+        part[p] = tot;
     }
+}
+__global__ __launch_bounds__(CH_BLK) void chamfer_term_kernel(const double *__restrict__ part, int P, double *term, const int *skip)
+{
+    VT_SKIP_RETURN(skip);
+    __shared__ double rs[CH_BLK];
+    double a = 0;
+    for (int k = threadIdx.x; k < P; k += CH_BLK) a += part[k];
+    rs[threadIdx.x] = a;
+    __syncthreads();
+    for (int o = CH_BLK / 2; o > 0; o >>= 1) { if (threadIdx.x < o) rs[threadIdx.x] += rs[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) atomicAdd(term, rs[0] / (double)P);
 }
 
 extern "C" int vt_chamfer_ragged(const float *x, const int *offx, const float *y, const int *offy, int P, float gscale, double *term,
                                  float *dx, float *dy, void *stream)
 {
     VT_REQUIRE(x && offx && y && offy && P > 0, "vt_chamfer_ragged: bad argument");
-    hipLaunchKernelGGL(chamfer_kernel, dim3(P), dim3(CH_BLK), 0, vt_stream(stream), x, offx, y, offy, P, gscale / (float)P, term, dx, dy, vt_skip_flag_of(vt_stream(stream)));
-    VT_LAUNCH_CHECK();
+    hipStream_t st = vt_stream(stream); const int *skip = vt_skip_flag_of(st);
+    double *part = nullptr;         // one share of the term per pair, stream-ordered scratch (the entry point has no workspace argument)
+    if (term) VT_HIP(hipMallocAsync(reinterpret_cast<void **>(&part), sizeof(double) * (size_t)P, st));
+    hipLaunchKernelGGL(chamfer_kernel, dim3(P), dim3(CH_BLK), 0, st, x, offx, y, offy, P, gscale / (float)P, part, dx, dy, skip);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && term) { hipLaunchKernelGGL(chamfer_term_kernel, dim3(1), dim3(CH_BLK), 0, st, part, P, term, skip); e = hipGetLastError(); }
+    if (part) { const hipError_t ef = hipFreeAsync(part, st); if (e == hipSuccess) e = ef; }
+    if (e != hipSuccess) VT_FAIL(VT_ERR_HIP, "vt_chamfer_ragged: %s", hipGetErrorString(e));
     return VT_OK;
 }
 
