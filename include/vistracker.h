@@ -700,7 +700,7 @@ int vt_sifnet_loss_head(const float *df, const float *pca, const float *parts, c
  *   layout of params; overwritten when accumulate == 0, added to otherwise (S stacks of maps share one buffer).  Sums over points: fp32 on the MFMA over at most
  *   chunk_points points of one frame (0 = the default, 2048; otherwise a multiple of 64 up to 16384), the chunk partials then in fp64 in the order (frame,
  *   chunk) and rounded to fp32 once.  The same inputs give the same bits on every call.  workspace: vt_decoder_weight_grads_ws_bytes(B, N, chunk_points) bytes
- *   (-1 on bad sizes), 16-byte aligned; nothing in it needs initialising, all of it is overwritten.  Nothing is computed for points or feature maps. */
+ *   (-1 on bad sizes), 16-byte aligned; nothing in it needs initialising, all of it is overwritten.  Nothing is computed for points or feature maps (vt_decoder_grads below adds the maps). */
 long vt_decoder_param_floats(void);
 long vt_decoder_param_offset(int head, int layer, int is_bias);
 int vt_decoder_train_forward(const float *params, const float *cam, const vt_maps *maps, const float *pts, const float *crop_center, const float *body_center,
@@ -709,6 +709,30 @@ long vt_decoder_weight_grads_ws_bytes(int B, int N, int chunk_points);
 int vt_decoder_weight_grads(const float *params, const float *cam, const vt_maps *maps, const float *pts, const float *crop_center, const float *body_center,
                             int B, int N, const float *d_df, const float *d_pca, const float *d_parts, const float *d_centers, const float *d_vis,
                             float *dparams, int accumulate, int chunk_points, void *workspace, void *stream);
+
+/* ---- the gradient to the eight feature maps, with or without the weight gradients (dectrain.hip, section 5): what loss.backward() of the reference's train step
+ * (trainer/trainer.py:97-106) sends on to the encoders through the sampled maps, i.e. the backward of model/geometry.py:4-14 (grid_sample, align_corners=True,
+ * zeros padding) applied to d_a0 = sum over the heads of W_h0^T delta_h1.  The map gradient is the only tensor that crosses from the decoders to the encoders.
+ *
+ * vt_decoder_grads takes the arguments of vt_decoder_weight_grads and, in addition, d_maps and accumulate_maps.  d_maps: eight NHWC gradient buffers in the
+ *   layout of `maps` (only maps[] and res[] are read); a NULL pointer skips that map, d_maps->res must equal maps->res (VT_ERR_ARG otherwise), the whole
+ *   argument may be NULL.  dparams may be NULL: then no weight gradient is computed.  Both NULL (or all eight pointers NULL with dparams NULL) is VT_ERR_ARG.
+ *   With d_maps NULL the call is vt_decoder_weight_grads, bit for bit (that entry is a call of this one).
+ * ARITHMETIC: d_a0 per point in exact fp32 products accumulated in fp32 on the f32-input MFMA, K = heads (0..4, live ones) x 128.  A point outside the image
+ *   still sends its gradient through the four non-df heads; only its d_df counts as zero.  Texel (y,x) of (frame, map) receives w_tap . d_a0[channels of the map]
+ *   from every point with an in-bounds tap on it, with the forward's own fp32 tap weights (in-bounds flags folded in, coordinates clamped to [-2, R+1]); the
+ *   products and the sum are fp64, rounded to fp32 once per slab (at most 8192 points, or one chunk).  Order of addition: the four base cells (y-1,x-1), (y-1,x),
+ *   (y,x-1), (y,x) in that order, ascending point index within each; across slabs slab order, which is (frame, chunk) order.  No atomics, one writer per
+ *   element per launch: the same inputs give the same bits on every call.  accumulate_maps == 0: every element of every requested map is written (zeros where no
+ *   tap lands); != 0: added onto what is there (S stacks share their tmpx tensors, chore_triplane.py:139-149, so their gradients add).  All five upstream
+ *   gradients NULL: requested maps get exact zeros, or are left alone when accumulating.
+ * workspace: vt_decoder_grads_ws_bytes(B, N, chunk_points, want_maps) bytes (-1 on bad sizes), 16-byte aligned: that of vt_decoder_weight_grads (d_a0 overwrites
+ *   a_0 in the tape once the weight-gradient GEMM of the slab is enqueued) and, with want_maps != 0, per map and tape row of a slab one 64-bit sort key (padded to
+ *   a power of two) and one 16-byte tap entry.  It does not depend on the maps' resolutions.  Nothing in it needs initialising. */
+long vt_decoder_grads_ws_bytes(int B, int N, int chunk_points, int want_maps);
+int vt_decoder_grads(const float *params, const float *cam, const vt_maps *maps, const float *pts, const float *crop_center, const float *body_center,
+                     int B, int N, const float *d_df, const float *d_pca, const float *d_parts, const float *d_centers, const float *d_vis,
+                     float *dparams, int accumulate, const vt_maps *d_maps, int accumulate_maps, int chunk_points, void *workspace, void *stream);
 
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two

@@ -156,6 +156,8 @@ SIGNATURES = {
     "vt_decoder_train_forward": (ci, [fp, vp, C.POINTER(VtMaps), fp, fp, fp, ci, ci, fp, fp, fp, fp, fp, vp]),
     "vt_decoder_weight_grads_ws_bytes": (cl, [ci, ci, ci]),
     "vt_decoder_weight_grads": (ci, [fp, vp, C.POINTER(VtMaps), fp, fp, fp, ci, ci, fp, fp, fp, fp, fp, fp, ci, ci, vp, vp]),
+    "vt_decoder_grads_ws_bytes": (cl, [ci, ci, ci, ci]),
+    "vt_decoder_grads": (ci, [fp, vp, C.POINTER(VtMaps), fp, fp, fp, ci, ci, fp, fp, fp, fp, fp, fp, ci, C.POINTER(VtMaps), ci, ci, vp, vp]),
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
 }

@@ -1,6 +1,6 @@
-// dectrain.hip -- training the five SIF-Net point decoders (model/chore.py:113-126 make_decoder) with the feature maps frozen: a forward from PLAIN
-// device weights (the flat parameter buffer an optimiser updates every step) and the gradient of the objective to every weight and bias
-// (what loss.backward() leaves in the decoders' .grad: trainer/trainer.py:97-106).  The query kernels (query.hip, query_f32.hip) cannot serve this: they
+// dectrain.hip -- training the five SIF-Net point decoders (model/chore.py:113-126 make_decoder): a forward from PLAIN device weights (the flat parameter
+// buffer an optimiser updates every step), the gradient of the objective to every weight and bias (what loss.backward() leaves in the decoders' .grad:
+// trainer/trainer.py:97-106) and, on request, its gradient to the eight feature maps (what the same backward hands on to the encoders; section 5 below).  The query kernels (query.hip, query_f32.hip) cannot serve this: they
 // hold the weights as fragment layouts packed on the host at vt_sifnet_create and never expose a hidden activation.
 //
 // PARAMETERS.  One flat fp32 buffer: for head h (df 2, pca 9, parts 14, centers 3, vis 1) and layer l = 0..3, W_hl (out,in) row-major (torch's
@@ -28,6 +28,8 @@
 // point (612 + 5 heads x (3 x 128 activations + 3 x 128 + 16 deltas)): a full tape of B = 8, N = 20 000 would be 2.9 GB, a slab is at most 297 MB (148 MB at
 // the default chunk).  Rows of a ragged last tile beyond N carry a_0 = 0 and delta = 0 (exact zeros in every product); tiles wholly beyond N are neither
 // written nor read.  Every workspace byte read was written by the same call.
+// vt_decoder_grads adds, per slab and after step 3, the map gradient: da0_kernel (d_a0 = sum_h W_h0^T delta_h1, over a_0 in the tape), tapkey_kernel, sort_kernel,
+// scatter_kernel -- described at section 5.  With dparams NULL steps 3 and 4 are not launched.
 //
 // DEFAULT chunk_points = 2048: 80 chunks at B = 8, N = 20 000 -> 12 000 one-wave GEMM tiles for 1024 SIMDs, 2.2 MB of partials per chunk.
 #include "common.h"
@@ -553,6 +555,198 @@ __global__ __launch_bounds__(256) void finish_kernel(const float *__restrict__ p
     dparams[p] = accumulate ? dparams[p] + (float)s : (float)s;
 }
 
+// ---- 5. the gradient to the feature maps ---------------------------------------------------------------------------------------------------------------
+// (model/geometry.py:4-14 backward: grid_sample's gradient to its input, align_corners=True, zeros padding.)  Per slab, after wgrad_kernel has been enqueued:
+//   a. da0_kernel    per 64-point tile: d_a0[612][64] = sum over the live heads, in the order 0..4, of W_h0^T (611 x 128) . delta_h1 (128 x 64), the transposed-slice
+//                    path of the delta propagation (exact fp32 products, fp32 accumulation on the MFMA, K = heads x 128).  d_a0 OVERWRITES a_0 in the tape (wgrad_kernel,
+//                    its last reader, is ahead in the stream).  The z_feat columns 256..258 and the pad column read zero weights and hold exact zeros; nobody reads them.
+//   b. tapkey_kernel per tile: the taps_setup entry of every (map, point) -> workspace, and one 64-bit key (frame << 42 | base cell << 20 | tape row) per (map, point),
+//                    all ones for rows beyond N, points without an in-bounds tap and maps that are not requested.  Tape rows ascend with (frame, point index).
+//   c. sort_kernel   one workgroup per map: bitonic sort of the slab's keys in LDS (at most 16384 keys, 128 KB).  The keys of live entries are unique, so the sorted
+//                    sequence does not depend on how it was reached: per (frame, cell) the points stand in ascending index.
+//   d. scatter_kernel per map, one wave per (frame, texel), lanes across the channels (one tap = one contiguous row of 128 .. 1024 B of d_a0): the lists of the four
+//                    cells (y-1,x-1), (y-1,x), (y,x-1), (y,x) are found by binary search (lanes 0..3, one list each) and walked in that order, each in ascending
+//                    point index.  Tap weights are the fp32 products of feat_value (in-bounds flags folded in), so the gradient is that of the forward's own linear
+//                    map; weight x d_a0 is an exact fp64 product, summed in fp64 and rounded to fp32 once per slab: FP64 BY CHOICE -- a texel may collect every point
+//                    of a slab, and the sequential fp32 chain of that length is the case that measured 4.4 .. 4.8 e32 for the bias gradients above.
+//                    The frame's first slab stores (accumulate_maps == 0: zeros where no tap lands, so every element is written once), later slabs and
+//                    accumulate_maps != 0 add, and then only texels that a tap lands on are touched.  Across slabs the order is slab order = (frame, chunk) order.
+// No floating-point atomics, no atomics at all; one writer per element per launch.
+struct GArgs {
+    float *dmaps[8];
+    unsigned long long *keys;   // [8][kcap]
+    int4 *taps;                 // [8][rows]
+    int kcap, ksort;            // key stride (a power of two >= rows); power of two >= the rows of this slab
+    int nrows, nchunks;         // rows and chunks of this slab
+    int accumulate;
+};
+
+#define KEY_NONE (~0ull)
+#define DA0_LDS_FLOATS (2 * HID * FS + 64 * HS)
+
+__device__ __forceinline__ int map_first_channel(int mi) { return mi == 0 ? 0 : (mi == 1 ? 259 : (mi < 5 ? 323 + 32 * (mi - 2) : 419 + 64 * (mi - 5))); }
+
+// a 128 x 32 slice of W0^T on its way to LDS: Wl[m][kk] = W0[(k0 + kk) 611 + c0 + m]; the z_feat and pad columns read as 0
+__device__ __forceinline__ void load_w0t(WReg &r, const float *__restrict__ W0, int c0, int k0, int tid)
+{
+    const int m = tid & 127, kk0 = tid >> 7, col = c0 + m;
+    const bool ok = col < KIN && !(col >= 256 && col < 259);
+#pragma unroll
+    for (int i = 0; i < 16; i++) r.v[i] = ok ? W0[(size_t)(k0 + kk0 + 2 * i) * KIN + col] : 0.f;
+}
+
+__global__ __launch_bounds__(256, 2) void da0_kernel(const TArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *Wl = lds;                                // 2 x [128][FS] slices of W0^T
+    float *H = Wl + 2 * HID * FS;                   // [64][HS] delta_1 of one head
+    int b, n0; long row0;
+    if (!tile_of_block(a, b, n0, row0)) return;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, j = lane & 15;
+    float *dst = a.tape + (size_t)row0 * KP;
+#pragma unroll 1
+    for (int mb = 0; mb < 5; mb++) {                // 128 feature columns a pass
+        Acc c;
+        acc_zero(c);
+#pragma unroll 1
+        for (int hs = 0; hs < a.nheads; hs++) {
+            const int hid = a.heads[hs];
+            const float *__restrict__ W0 = a.params + a.off.w[hid][0];
+            const float *__restrict__ D = tape_part(a, hid, 3) + (size_t)row0 * HID;
+            __syncthreads();                        // every wave is past its reads of H and of both slice buffers
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const int e = tid + 256 * i, row = e >> 5, c4 = (e & 31) * 4;
+                *reinterpret_cast<float4 *>(H + row * HS + c4) = *reinterpret_cast<const float4 *>(D + (size_t)row * HID + c4);
+            }
+            WReg r;
+            load_w0t(r, W0, 128 * mb, 0, tid);
+#pragma unroll 1
+            for (int s = 0; s < 4; s++) {
+                float *buf = Wl + (s & 1) * HID * FS;
+                store_w<true>(r, buf, tid);
+                __syncthreads();
+                if (s + 1 < 4) load_w0t(r, W0, 128 * mb, 32 * (s + 1), tid);
+                mma_slice<4>(c, buf, H + 32 * s, HS, wave, q, j);
+            }
+        }
+#pragma unroll
+        for (int mt = 0; mt < 2; mt++) {
+            const int col = 128 * mb + (2 * wave + mt) * 16 + q * 4;
+            if (col < KP) {
+#pragma unroll
+                for (int nt = 0; nt < 4; nt++)
+                    *reinterpret_cast<float4 *>(dst + (size_t)(nt * 16 + j) * KP + col) = make_float4(c.v[mt][nt][0], c.v[mt][nt][1], c.v[mt][nt][2], c.v[mt][nt][3]);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void tapkey_kernel(const TArgs a, const GArgs g)
+{
+    __shared__ float sPt[64 * 3];
+    __shared__ int sIn[64];
+    __shared__ float sUV[4 * 64 * 2];
+    __shared__ int4 sTap[8 * 64];
+    int b, n0; long row0;
+    const int tid = threadIdx.x;
+    if (!tile_of_block(a, b, n0, row0)) {           // a tile wholly beyond N: its tape rows were never written, its keys say so
+        for (int e = tid; e < 512; e += 256) g.keys[(size_t)(e >> 6) * g.kcap + row0 + (e & 63)] = KEY_NONE;
+        return;
+    }
+    project_tile(a, b, n0, tid, sPt, sIn, sUV);
+    __syncthreads();
+    taps_setup(a, sUV, sTap, tid);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const int e = tid + 256 * i, mi = e >> 6, pt = e & 63;
+        const int4 t = sTap[e];
+        const long row = row0 + pt;
+        const bool live = n0 + pt < a.N && (t.y >> 2) != 0 && g.dmaps[mi] != nullptr;
+        const unsigned long long cell = (unsigned long long)(t.x / map_channels(mi));
+        g.keys[(size_t)mi * g.kcap + row] = live ? ((unsigned long long)b << 42) | (cell << 20) | (unsigned long long)row : KEY_NONE;
+        g.taps[(size_t)mi * a.rows + row] = t;
+    }
+}
+
+__global__ __launch_bounds__(1024) void sort_kernel(const GArgs g)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned long long skey[];
+    const int mi = blockIdx.x, tid = threadIdx.x, n = g.ksort;
+    if (!g.dmaps[mi]) return;
+    unsigned long long *K = g.keys + (size_t)mi * g.kcap;
+    for (int i = tid; i < n; i += 1024) skey[i] = i < g.nrows ? K[i] : KEY_NONE;
+    for (int k = 2; k <= n; k <<= 1)
+        for (int jj = k >> 1; jj > 0; jj >>= 1) {
+            __syncthreads();
+            for (int t = tid; t < (n >> 1); t += 1024) {
+                const int lo = ((t & ~(jj - 1)) << 1) | (t & (jj - 1)), hi = lo | jj;
+                const unsigned long long x = skey[lo], y = skey[hi];
+                if ((x > y) == ((lo & k) == 0)) { skey[lo] = y; skey[hi] = x; }
+            }
+        }
+    __syncthreads();
+    for (int i = tid; i < n; i += 1024) K[i] = skey[i];
+}
+
+__global__ __launch_bounds__(256) void scatter_kernel(const TArgs a, const GArgs g, int mi)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int R = a.res[mi], C = map_channels(mi), n = g.ksort;
+    const long texel = (long)blockIdx.x * 4 + wave;
+    if (texel >= (long)R * R) return;
+    const int y = (int)(texel / R), x = (int)(texel % R);
+    const int f0 = a.g0 / a.nc, b = f0 + blockIdx.y;
+    const long first = (long)b * a.nc;              // the frame's first chunk lies in exactly one slab: that one stores
+    const bool store = !g.accumulate && first >= a.g0 && first < (long)a.g0 + g.nchunks;
+    const unsigned long long *__restrict__ K = g.keys + (size_t)mi * g.kcap;
+    const int4 *__restrict__ T = g.taps + (size_t)mi * a.rows;
+    const float *__restrict__ dA = a.tape + map_first_channel(mi);
+
+    // lanes 0..3: the start of the list of cell (y - 1, x - 1), (y - 1, x), (y, x - 1), (y, x)
+    const int l4 = lane & 3, cy = y - (l4 < 2 ? 1 : 0), cx = x - ((l4 & 1) == 0 ? 1 : 0);
+    const unsigned long long prefix = ((unsigned long long)b << 22) | (unsigned long long)(unsigned)(max(cy, 0) * R + max(cx, 0));
+    int pos = 0;
+    for (int step = n >> 1; step > 0; step >>= 1) if ((K[pos + step - 1] >> 20) < prefix) pos += step;
+    if ((K[pos] >> 20) < prefix) pos++;
+    if (cy < 0 || cx < 0) pos = n;
+
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    bool touched = false;
+#pragma unroll 1
+    for (int l = 0; l < 4; l++) {
+        const int ly = y - (l < 2 ? 1 : 0), lx = x - ((l & 1) == 0 ? 1 : 0);
+        const unsigned long long pf = ((unsigned long long)b << 22) | (unsigned long long)(unsigned)(max(ly, 0) * R + max(lx, 0));
+#pragma unroll 1
+        for (int i = __shfl(pos, l, 64); i < n; i++) {
+            const unsigned long long key = K[i];
+            if ((key >> 20) != pf) break;
+            const long row = (long)(key & 0xFFFFFull);
+            const int4 t = T[row];
+            const int dxf = t.y & 1, dyf = (t.y >> 1) & 1, ib = t.y >> 2;
+            const float wx1 = __int_as_float(t.z), wy1 = __int_as_float(t.w), wx0 = 1.0f - wx1, wy0 = 1.0f - wy1;
+#pragma unroll
+            for (int tap = 0; tap < 4; tap++) {
+                const int tx = tap & 1, ty = tap >> 1;
+                if (!((ib >> tap) & 1) || ly + ty * dyf != y || lx + tx * dxf != x) continue;
+                const double w = (double)((tx ? wx1 : wx0) * (ty ? wy1 : wy0));
+                const float *__restrict__ src = dA + (size_t)row * KP;
+#pragma unroll
+                for (int s = 0; s < 4; s++) { const int c = lane + 64 * s; if (c < C) acc[s] += w * (double)src[c]; }
+                touched = true;
+            }
+        }
+    }
+    if (!store && !touched) return;
+    float *out = g.dmaps[mi] + (((size_t)b * R + y) * R + x) * C;
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int c = lane + 64 * s;
+        if (c < C) out[c] = store ? (float)acc[s] : out[c] + (float)acc[s];
+    }
+}
+
 static int fill_common(TArgs &a, const float *params, const float *cam, const vt_maps *maps, const float *pts, const float *cc, const float *bc, int B, int N,
                        const char *who)
 {
@@ -617,25 +811,40 @@ int vt_decoder_train_forward(const float *params, const float *cam, const vt_map
     return VT_OK;
 }
 
-long vt_decoder_weight_grads_ws_bytes(int B, int N, int chunk_points)
+static long pow2_ceil(long n) { long p = 2; while (p < n) p <<= 1; return p; }
+static long align16(long n) { return (n + 15) & ~15L; }
+static long grads_ws_bytes(int B, int N, int chunk_points, int want_maps, dect::Plan &p)
 {
-    dect::Plan p;
     if (!dect::make_plan(p, B, N, chunk_points)) return -1;
-    return p.run_bytes + p.tape_bytes + p.part_bytes;
+    long n = p.run_bytes + p.tape_bytes + p.part_bytes;
+    if (want_maps) n = align16(n) + 8 * pow2_ceil(p.rows) * 8 + 8 * p.rows * 16;      // the sort keys and the tap entries of a slab, per map
+    return n;
 }
 
-int vt_decoder_weight_grads(const float *params, const float *cam, const vt_maps *maps, const float *pts, const float *crop_center, const float *body_center,
-                            int B, int N, const float *d_df, const float *d_pca, const float *d_parts, const float *d_centers, const float *d_vis,
-                            float *dparams, int accumulate, int chunk_points, void *workspace, void *stream)
+long vt_decoder_weight_grads_ws_bytes(int B, int N, int chunk_points) { dect::Plan p; return grads_ws_bytes(B, N, chunk_points, 0, p); }
+long vt_decoder_grads_ws_bytes(int B, int N, int chunk_points, int want_maps) { dect::Plan p; return grads_ws_bytes(B, N, chunk_points, want_maps, p); }
+
+static int decoder_grads(const char *who, const float *params, const float *cam, const vt_maps *maps, const float *pts, const float *crop_center,
+                         const float *body_center, int B, int N, const float *const gs[5], float *dparams, int accumulate, const vt_maps *d_maps,
+                         int accumulate_maps, int chunk_points, void *workspace, void *stream)
 {
     using namespace dect;
     Plan p;
-    VT_REQUIRE(make_plan(p, B, N, chunk_points), "vt_decoder_weight_grads: B = %d (1 .. 65535), N = %d, chunk_points = %d (0, or a multiple of 64 up to %d)", B, N,
+    VT_REQUIRE(make_plan(p, B, N, chunk_points), "%s: B = %d (1 .. 65535), N = %d, chunk_points = %d (0, or a multiple of 64 up to %d)", who, B, N,
                chunk_points, MAX_CHUNK);
-    TArgs a; int rc = fill_common(a, params, cam, maps, pts, crop_center, body_center, B, N, "vt_decoder_weight_grads"); if (rc) return rc;
-    VT_REQUIRE(dparams && workspace && (reinterpret_cast<size_t>(workspace) & 15) == 0, "vt_decoder_weight_grads: dparams or workspace null, or workspace not 16-byte aligned");
+    TArgs a; int rc = fill_common(a, params, cam, maps, pts, crop_center, body_center, B, N, who); if (rc) return rc;
+    GArgs g;
+    memset(&g, 0, sizeof(g));
+    bool want_maps = false;
+    if (d_maps)
+        for (int i = 0; i < 8; i++) {
+            VT_REQUIRE(d_maps->res[i] == maps->res[i], "%s: d_maps->res[%d] = %d, the map's is %d", who, i, d_maps->res[i], maps->res[i]);
+            g.dmaps[i] = const_cast<float *>(d_maps->maps[i]);      /* vt_maps serves inputs elsewhere, hence its const */
+            want_maps = want_maps || g.dmaps[i];
+        }
+    VT_REQUIRE(dparams || want_maps, "%s: neither dparams nor a map gradient requested", who);
+    VT_REQUIRE(workspace && (reinterpret_cast<size_t>(workspace) & 15) == 0, "%s: workspace null or not 16-byte aligned", who);
     hipStream_t st = vt_stream(stream);
-    const float *gs[5] = {d_df, d_pca, d_parts, d_centers, d_vis};
     unsigned live = 0;
     for (int i = 0; i < 5; i++) if (gs[i]) { a.gout[i] = gs[i]; a.heads[a.nheads++] = i; live |= 1u << i; }
     const long P = param_floats();
@@ -643,15 +852,30 @@ int vt_decoder_weight_grads(const float *params, const float *cam, const vt_maps
     double *run = reinterpret_cast<double *>(ws);
     a.tape = reinterpret_cast<float *>(ws + p.run_bytes); a.rows = p.rows;
     float *partials = reinterpret_cast<float *>(ws + p.run_bytes + p.tape_bytes);
+    g.kcap = (int)pow2_ceil(p.rows);
+    g.keys = reinterpret_cast<unsigned long long *>(ws + align16(p.run_bytes + p.tape_bytes + p.part_bytes));
+    g.taps = reinterpret_cast<int4 *>(g.keys + 8L * g.kcap);
+    g.accumulate = accumulate_maps;
     a.chunk = p.chunk; a.nc = p.nc;
     const unsigned fin_blocks = (unsigned)((P + 255) / 256);
-    if (a.nheads == 0) {        // every upstream gradient NULL: the gradient is exactly zero
-        hipLaunchKernelGGL(finish_kernel, dim3(fin_blocks), dim3(256), 0, st, partials, P, 0, run, 1, 1, dparams, accumulate, a.off, 0u);
-        VT_LAUNCH_CHECK();
+    if (a.nheads == 0) {        // every upstream gradient NULL: the gradients are exactly zero
+        if (dparams) {
+            hipLaunchKernelGGL(finish_kernel, dim3(fin_blocks), dim3(256), 0, st, partials, P, 0, run, 1, 1, dparams, accumulate, a.off, 0u);
+            VT_LAUNCH_CHECK();
+        }
+        for (int i = 0; i < 8 && !accumulate_maps; i++)
+            if (g.dmaps[i]) {
+                const hipError_t e = hipMemsetAsync(g.dmaps[i], 0, sizeof(float) * (size_t)B * a.res[i] * a.res[i] * (i == 0 ? 256 : (i == 1 ? 64 : (i < 5 ? 32 : 64))), st);
+                if (e != hipSuccess) VT_FAIL(VT_ERR_HIP, "%s: memset -> %s", who, hipGetErrorString(e));
+            }
         return VT_OK;
     }
-    const size_t lds = sizeof(float) * MLP_LDS_FLOATS;
+    const size_t lds = sizeof(float) * MLP_LDS_FLOATS, lds_da0 = sizeof(float) * DA0_LDS_FLOATS;
     VT_LDS_LIMIT((mlp_kernel<1>), lds);
+    if (want_maps) {
+        VT_LDS_LIMIT(da0_kernel, lds_da0);
+        VT_LDS_LIMIT(sort_kernel, sizeof(unsigned long long) * (size_t)MAX_CHUNK);      // the largest slab there is: rows <= max(SLAB_POINTS, MAX_CHUNK)
+    }
     for (long g0 = 0; g0 < p.total; g0 += p.slab) {
         const int n = (int)(p.total - g0 < p.slab ? p.total - g0 : p.slab);
         a.g0 = (int)g0;
@@ -660,13 +884,49 @@ int vt_decoder_weight_grads(const float *params, const float *cam, const vt_maps
         VT_LAUNCH_CHECK();
         hipLaunchKernelGGL((mlp_kernel<1>), dim3(tiles, a.nheads), dim3(256), lds, st, a);
         VT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(wgrad_kernel, dim3(WG_TILES, a.nheads, n), dim3(64), 0, st, a, partials, P);
+        if (dparams) {
+            hipLaunchKernelGGL(wgrad_kernel, dim3(WG_TILES, a.nheads, n), dim3(64), 0, st, a, partials, P);
+            VT_LAUNCH_CHECK();
+            hipLaunchKernelGGL(finish_kernel, dim3(fin_blocks), dim3(256), 0, st, partials, P, n, run, g0 == 0 ? 1 : 0, g0 + n >= p.total ? 1 : 0, dparams, accumulate,
+                               a.off, live);
+            VT_LAUNCH_CHECK();
+        }
+        if (!want_maps) continue;
+        g.nrows = n * p.chunk; g.nchunks = n; g.ksort = (int)pow2_ceil(g.nrows);
+        hipLaunchKernelGGL(da0_kernel, dim3(tiles), dim3(256), lds_da0, st, a);       // overwrites a_0: wgrad_kernel is ahead in the stream
         VT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(finish_kernel, dim3(fin_blocks), dim3(256), 0, st, partials, P, n, run, g0 == 0 ? 1 : 0, g0 + n >= p.total ? 1 : 0, dparams, accumulate,
-                           a.off, live);
+        hipLaunchKernelGGL(tapkey_kernel, dim3(tiles), dim3(256), 0, st, a, g);
         VT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(sort_kernel, dim3(8), dim3(1024), sizeof(unsigned long long) * (size_t)g.ksort, st, g);
+        VT_LAUNCH_CHECK();
+        const unsigned frames = (unsigned)((g0 + n - 1) / p.nc - g0 / p.nc + 1);
+        for (int mi = 0; mi < 8; mi++) {
+            if (!g.dmaps[mi]) continue;
+            const long texels = (long)a.res[mi] * a.res[mi];
+            hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)((texels + 3) / 4), frames), dim3(256), 0, st, a, g, mi);
+            VT_LAUNCH_CHECK();
+        }
     }
     return VT_OK;
+}
+
+int vt_decoder_weight_grads(const float *params, const float *cam, const vt_maps *maps, const float *pts, const float *crop_center, const float *body_center,
+                            int B, int N, const float *d_df, const float *d_pca, const float *d_parts, const float *d_centers, const float *d_vis,
+                            float *dparams, int accumulate, int chunk_points, void *workspace, void *stream)
+{
+    VT_REQUIRE(dparams, "vt_decoder_weight_grads: dparams null");
+    const float *gs[5] = {d_df, d_pca, d_parts, d_centers, d_vis};
+    return decoder_grads("vt_decoder_weight_grads", params, cam, maps, pts, crop_center, body_center, B, N, gs, dparams, accumulate, nullptr, 0, chunk_points, workspace,
+                         stream);
+}
+
+int vt_decoder_grads(const float *params, const float *cam, const vt_maps *maps, const float *pts, const float *crop_center, const float *body_center,
+                     int B, int N, const float *d_df, const float *d_pca, const float *d_parts, const float *d_centers, const float *d_vis,
+                     float *dparams, int accumulate, const vt_maps *d_maps, int accumulate_maps, int chunk_points, void *workspace, void *stream)
+{
+    const float *gs[5] = {d_df, d_pca, d_parts, d_centers, d_vis};
+    return decoder_grads("vt_decoder_grads", params, cam, maps, pts, crop_center, body_center, B, N, gs, dparams, accumulate, d_maps, accumulate_maps, chunk_points,
+                         workspace, stream);
 }
 
 }  // extern "C"

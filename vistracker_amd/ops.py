@@ -679,7 +679,7 @@ def sifnet_loss_head(preds, df_h, df_o, parts_gt, pca_gt, obj_center, visibility
 
 
 # --------------------------------------------------------------------------------------------------
-# training the point decoders, feature maps frozen (csrc/dectrain.hip)
+# training the point decoders, with or without the gradient to the feature maps (csrc/dectrain.hip)
 # --------------------------------------------------------------------------------------------------
 STATE_DICT_MODULES = {"df": "df", "pca": "pca_predictor", "parts": "part_predictor", "centers": "center_predictor", "vis": "visib_predictor"}
 STATE_DICT_LAYERS = (0, 2, 4, 6)                               # the Conv1d entries of make_decoder's Sequential (chore.py:113-126)
@@ -762,14 +762,13 @@ def _train_maps(maps):
     maps = [maps] if isinstance(maps, FeatureMaps) else list(maps)
     if not maps or not all(isinstance(m, FeatureMaps) for m in maps):
         raise L.VtError("sifnet_query_train: maps is a FeatureMaps or a list of them, one per stack")
-    if any(t.requires_grad for m in maps for t in m.t):
-        raise L.VtError("sifnet_query_train: the feature maps are frozen here; a map that requires grad would silently get none")
     return maps
 
 
 class _QueryTrainFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, flat, cam, maps, pts, cc, bc, chunk_points):
+    def forward(ctx, flat, cam, maps, pts, cc, bc, chunk_points, *map_tensors):
+        # map_tensors: the 8 S tensors of ``maps`` in stack order, here only so that autograd sees them as inputs; the kernels read them through maps[s].c
         B, N = pts.shape[:2]
         outs = []
         with torch.cuda.device(flat.device):
@@ -787,21 +786,43 @@ class _QueryTrainFn(torch.autograd.Function):
     def backward(ctx, *gs):
         flat, pts, cc, bc = ctx.saved_tensors
         B, N = pts.shape[:2]
+        want_w, want_m = ctx.needs_input_grad[0], ctx.needs_input_grad[7:]
+        lib = L.lib()
         with torch.cuda.device(flat.device):
-            dflat = torch.empty_like(flat)
-            ws = torch.empty(int(L.lib().vt_decoder_weight_grads_ws_bytes(B, N, ctx.chunk)) // 4 + 4, device=flat.device)
+            dflat = torch.empty_like(flat) if want_w else None
+            dmaps = [None] * len(want_m)
+            if not any(want_m):                                # the maps are data: the weight-gradient entry, as before
+                ws = torch.empty(int(lib.vt_decoder_weight_grads_ws_bytes(B, N, ctx.chunk)) // 4 + 4, device=flat.device)
+            else:
+                ws = torch.empty(int(lib.vt_decoder_grads_ws_bytes(B, N, ctx.chunk, 1)) // 4 + 4, device=flat.device)
             for s, m in enumerate(ctx.maps):
                 g = [None if t is None else _f32(t) for t in gs[5 * s:5 * s + 5]]
-                L.check(L.lib().vt_decoder_weight_grads(L.dptr(flat), ctx.cam.ctypes.data, C.byref(m.c), L.dptr(pts), L.dptr(cc), L.dptr(bc), B, N,
-                                                        *[L.dptr(t) for t in g], L.dptr(dflat), 1 if s else 0, int(ctx.chunk), L.dptr(ws), L.stream_ptr()))
-        return dflat, None, None, None, None, None, None
+                if not any(want_m):
+                    if want_w:
+                        L.check(lib.vt_decoder_weight_grads(L.dptr(flat), ctx.cam.ctypes.data, C.byref(m.c), L.dptr(pts), L.dptr(cc), L.dptr(bc), B, N,
+                                                            *[L.dptr(t) for t in g], L.dptr(dflat), 1 if s else 0, int(ctx.chunk), L.dptr(ws), L.stream_ptr()))
+                    continue
+                # weights and maps of the stack from ONE call: the tape is built once.  A tensor two stacks share gets one buffer per stack; autograd adds them.
+                dm = L.VtMaps()
+                for i, t in enumerate(m.t):
+                    dm.res[i] = t.shape[1]
+                    if want_m[8 * s + i]:
+                        dmaps[8 * s + i] = torch.empty_like(t)
+                        dm.maps[i] = dmaps[8 * s + i].data_ptr()
+                if not want_w and not any(want_m[8 * s:8 * s + 8]):
+                    continue
+                L.check(lib.vt_decoder_grads(L.dptr(flat), ctx.cam.ctypes.data, C.byref(m.c), L.dptr(pts), L.dptr(cc), L.dptr(bc), B, N,
+                                             *[L.dptr(t) for t in g], L.dptr(dflat), 1 if s else 0, C.byref(dm), 0, int(ctx.chunk), L.dptr(ws), L.stream_ptr()))
+        return (dflat, None, None, None, None, None, None, *dmaps)
 
 
-def sifnet_query_train(params: DecoderParams, maps, pts, crop_center, body_center, chunk_points=0):
+def sifnet_query_train(params: DecoderParams, maps, pts, crop_center, body_center, chunk_points=0, train_decoders=True):
     """The query of a training step (chore_triplane.py:97-164 in train mode) from the plain weights of ``params``: ``maps`` is one ``FeatureMaps`` or a list of
     S, one per hourglass stack (they share their tmpx tensors, chore_triplane.py:139-149).  -> a list of S (df (B,2,N), pca (B,3,3,N), parts (B,14,N), centers
-    (B,3,N), vis (B,1,N)) tuples, the shape of ``intermediate_preds_list``.  Backward: one vt_decoder_weight_grads call per stack into ONE flat gradient
-    (``params.flat.grad``).  Points and maps are data here: there is no gradient for them, and one that requires grad raises."""
+    (B,3,N), vis (B,1,N)) tuples, the shape of ``intermediate_preds_list``.  Backward: one call per stack, into ONE flat gradient (``params.flat.grad``) and into
+    ``t.grad`` of every map tensor that requires grad (NHWC, as the tensor; a tensor two stacks share receives the sum) -- the gradient an encoder's backward
+    continues from.  With no map requiring grad the call is vt_decoder_weight_grads, otherwise vt_decoder_grads (weights and maps from one tape).
+    ``train_decoders=False``: the decoders are data, only the maps receive a gradient.  The points are data here: one that requires grad raises."""
     maps = _train_maps(maps)
     if not isinstance(params, DecoderParams):
         raise L.VtError("sifnet_query_train: params is an ops.DecoderParams")
@@ -815,7 +836,8 @@ def sifnet_query_train(params: DecoderParams, maps, pts, crop_center, body_cente
     if pts.dim() != 3 or pts.shape[2] != 3 or tuple(cc.shape) != (B, 2) or tuple(bc.shape) != (B, 3) or any(m.B != B for m in maps):
         raise L.VtError(f"sifnet_query_train: points (B,N,3), crop_center (B,2), body_center (B,3), maps of B frames; got {tuple(pts.shape)}, {tuple(cc.shape)}, "
                         f"{tuple(bc.shape)}, {[m.B for m in maps]}")
-    outs = _QueryTrainFn.apply(params.flat, params.cam, maps, pts, cc, bc, int(chunk_points))
+    flat = params.flat if train_decoders else params.flat.detach()
+    outs = _QueryTrainFn.apply(flat, params.cam, maps, pts, cc, bc, int(chunk_points), *[t for m in maps for t in m.t])
     return [(outs[5 * s], outs[5 * s + 1].view(B, 3, 3, N), outs[5 * s + 2], outs[5 * s + 3], outs[5 * s + 4]) for s in range(len(maps))]
 
 

@@ -86,7 +86,8 @@ class SIFNetQuery:
         """The query of a training step from the plain weights of ``params`` (an ``ops.DecoderParams``; this network's packed handle is not used): sets
         ``preds`` and ``intermediate_preds_list`` as the reference's train-mode query does (chore_triplane.py:137-163), one tuple per stack.  ``maps``: a
         ``FeatureMaps`` or a list of S of them (default: the maps set on this network, one stack).  ``get_errors`` then works unchanged and
-        ``error.backward()`` fills ``params.flat.grad``; the points and the maps get no gradient."""
+        ``error.backward()`` fills ``params.flat.grad`` and the ``.grad`` of every map tensor that requires grad (``train_decoders=False``: of the maps
+        only); the points get no gradient."""
         maps = self.maps if maps is None else maps
         assert maps is not None, "call set_feature_maps() (or filter()) first, or pass maps"
         self.points, self.crop_center = points, crop_center

@@ -104,16 +104,20 @@ class DecoderTrainer:
         self.params = ops.DecoderParams.from_decoders(net.decoders, cam=net.camera.as_cam5(), device=net.device)
         self.optimizer = ops.FusedAdam([self.params.flat], lr=lr)
 
-    def train_step(self, batch, crop_center, maps=None):
+    def train_step(self, batch, crop_center, maps=None, train_decoders=True):
         """one step on a batch of ``make_training_batch``: zero_grad, query, get_errors, backward, Adam.  ``maps``: a ``FeatureMaps`` or a list of S, one per
-        stack (default: the maps set on ``net``).  -> (error (), losses_all (6,)): float64 device tensors of the step's objective BEFORE the update; nothing
+        stack (default: the maps set on ``net``).  Map tensors that require grad receive (accumulate, as any leaf) their ``.grad`` from the same backward; what
+        steps them -- an encoder's backward, an optimiser of the caller's -- is the caller's.  ``train_decoders=False``: the decoders are data, only the maps
+        get a gradient and there is no Adam step.  -> (error (), losses_all (6,)): float64 device tensors of the step's objective BEFORE the update; nothing
         here synchronises."""
-        self.optimizer.zero_grad()
-        self.net.query_train(self.params, batch["points"], crop_center=crop_center, body_center=batch["body_center"], maps=maps)
+        if train_decoders:
+            self.optimizer.zero_grad()
+        self.net.query_train(self.params, batch["points"], crop_center=crop_center, body_center=batch["body_center"], maps=maps, train_decoders=train_decoders)
         error, losses_all = self.net.get_errors(batch["df_h"], batch["df_o"], batch["labels"], batch["pca_axis"], self.max_dist, batch["body_center"],
                                                 batch["obj_center"], visibility=batch["visibility"])
         error.backward()
-        self.optimizer.step()
+        if train_decoders:
+            self.optimizer.step()
         return error.detach(), losses_all
 
     def state_dict(self, prefix=""):
