@@ -734,6 +734,51 @@ int vt_decoder_grads(const float *params, const float *cam, const vt_maps *maps,
                      int B, int N, const float *d_df, const float *d_pca, const float *d_parts, const float *d_centers, const float *d_vis,
                      float *dparams, int accumulate, const vt_maps *d_maps, int accumulate_maps, int chunk_points, void *workspace, void *stream);
 
+/* ---- the backward of the encoders' ConvBlock (convtrain.hip): model/net_util.py:346-396, the unit conv2 / conv3 / conv4, every b1 / b2 / b2_plus / b3 of an
+ * hourglass and every top_m are built from (model/HGFilters.py:4-203).  All tensors are NHWC fp32 channel slices (pointer, channel stride, channel offset; stride
+ * and offset multiples of 4, pointers 16-byte aligned), weights plain fp32 device memory in the reference's (Cout, Cin, kh, kw) layout.  H % 8 == 0, W % 16 == 0,
+ * B <= 65535.  ARITHMETIC: exact fp32 products accumulated in fp32 on the f32-input MFMA, no range assumption on a gradient (scaling d_out by a power of two scales
+ * every result by it, bit for bit); no atomics, one writer per element per launch, fixed summation order: the same inputs give the same bits on every call.
+ * Nothing in a workspace needs initialising.  `accumulate` != 0 adds onto the PARAMETER gradients (dW, dgamma, dbeta), 0 overwrites them.
+ *
+ * vt_conv3x3_dgrad (net_util.py:379, 383, 387, backward to the convolution's input; nn.Conv2d 3x3 / stride 1 / pad 1, bias-free: net_util.py:213-216):
+ *   d_in[b,y,x,ci] = sum (co,ky,kx) W[co,ci,ky,kx] d_out[b,y-ky+1,x-kx+1,co], zero outside the image.  Cout in {32, 64, 128}, Cin % 32 == 0, Cin <= 256.
+ *   workspace: vt_conv_dgrad_workspace_bytes(cout, cin, 9) (the weights in fragment order, rewritten by every call).
+ * vt_conv3x3_wgrad (the same lines, backward to the weight): dW[co,ci,ky,kx] = sum (b,y,x) d_out[b,y,x,co] a[b,y+ky-1,x+kx-1,ci] with
+ *   a = max((x_in - mean) rstd gamma + beta, 0) recomputed from x_in and gn_stats (B x groups {mean, rstd} float pairs, as vt_groupnorm_finalize leaves them) with
+ *   the forward's own fp32 expression while the operand is staged (net_util.py:377-378, 381-382, 385-386); gn_stats NULL: a = x_in.  Split K over pixel tiles, the
+ *   partials added in fp64 in (frame, split) order and rounded once.  workspace: vt_conv_wgrad_workspace_bytes(B, H, W, cout, cin, 9).
+ * vt_conv1x1_dgrad / vt_conv1x1_wgrad: the same for the ConvBlock's projection (net_util.py:364-370, 391-392), Cout in {64, 128, 256}; workspaces with taps = 1.
+ * vt_gn_relu_backward (nn.GroupNorm + F.relu, net_util.py:358-362, 377-386): g = the gradient to the rectified activation, m = [xhat gamma + beta > 0] evaluated
+ *   with the forward's staging expression, n = HW C / groups:  dbeta = sum g m, dgamma = sum g m xhat, s1 = sum g m gamma, s2 = sum g m gamma xhat per (frame,
+ *   group), d_x = base + rstd (g m gamma - (s1 + xhat s2) / n).  base: the slice holding the other contributions to that tensor (may be d_x itself: add in place;
+ *   NULL: none).  d_x, dgamma, dbeta may each be NULL.  Sums and the element formula in fp64, fixed order.  workspace: vt_gn_relu_backward_workspace_bytes.
+ * vt_conv_block_backward (net_util.py:374-396 backward): dy (B,H,W,c1+c2+c3); x (B,H,W,cin) the block input; raw (B,H,W,c1+c2) = o1 | o2 as the forward's
+ *   convolutions wrote them; stats1..3 the {mean, rstd} areas of bn1 (of x), bn2 (of o1), bn3 (of o2); w1..3, gamma / beta 1..3 the parameters; wproj (c1+c2+c3,
+ *   cin), gamma4, beta4 the projection (bn4 shares stats1) or NULL for the identity residual (then cin == c1+c2+c3).  Outputs: d_x (B,H,W,cin), dW1..3, dgamma /
+ *   dbeta 1..4, dWproj; any may be NULL to skip it.  workspace: vt_conv_block_backward_workspace(B, H, W, cin, c1, c2, c3) bytes (-1 on bad sizes). */
+long vt_conv_dgrad_workspace_bytes(int cout, int cin, int taps);
+long vt_conv_wgrad_workspace_bytes(int B, int H, int W, int cout, int cin, int taps);
+long vt_gn_relu_backward_workspace_bytes(int B, int HW, int C, int groups);
+int vt_conv3x3_dgrad(const float *weight, int cout, int cin, const float *d_out, int do_cstride, int do_coff, int B, int H, int W,
+                     float *d_in, int di_cstride, int di_coff, void *workspace, void *stream);
+int vt_conv1x1_dgrad(const float *weight, int cout, int cin, const float *d_out, int do_cstride, int do_coff, int B, int H, int W,
+                     float *d_in, int di_cstride, int di_coff, void *workspace, void *stream);
+int vt_conv3x3_wgrad(const float *d_out, int do_cstride, int do_coff, const float *x_in, int xi_cstride, int xi_coff, const float *gn_stats, const float *gamma,
+                     const float *beta, int groups, int B, int H, int W, int cin, int cout, float *dW, int accumulate, void *workspace, void *stream);
+int vt_conv1x1_wgrad(const float *d_out, int do_cstride, int do_coff, const float *x_in, int xi_cstride, int xi_coff, const float *gn_stats, const float *gamma,
+                     const float *beta, int groups, int B, int H, int W, int cin, int cout, float *dW, int accumulate, void *workspace, void *stream);
+int vt_gn_relu_backward(const float *g, int g_cstride, int g_coff, const float *x_in, int x_cstride, int x_coff, const float *gn_stats, const float *gamma,
+                        const float *beta, int groups, int B, int HW, int C, const float *base, int base_cstride, int base_coff,
+                        float *d_x, int dx_cstride, int dx_coff, float *dgamma, float *dbeta, int accumulate, void *workspace, void *stream);
+long vt_conv_block_backward_workspace(int B, int H, int W, int cin, int c1, int c2, int c3);
+int vt_conv_block_backward(const float *dy, const float *x, const float *raw, const float *stats1, const float *stats2, const float *stats3,
+                           const float *w1, const float *w2, const float *w3, const float *gamma1, const float *gamma2, const float *gamma3,
+                           const float *beta1, const float *beta2, const float *beta3, const float *wproj, const float *gamma4, const float *beta4,
+                           int B, int H, int W, int cin, int c1, int c2, int c3,
+                           float *d_x, float *dW1, float *dW2, float *dW3, float *dgamma1, float *dbeta1, float *dgamma2, float *dbeta2, float *dgamma3, float *dbeta3,
+                           float *dgamma4, float *dbeta4, float *dWproj, void *workspace, int accumulate, void *stream);
+
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two
  * workgroups of 256 threads per CU, non-trivial operands), out[1] = shader clock sustained during it (MHz: s_memtime against the 100 MHz s_memrealtime),

@@ -158,6 +158,17 @@ SIGNATURES = {
     "vt_decoder_weight_grads": (ci, [fp, vp, C.POINTER(VtMaps), fp, fp, fp, ci, ci, fp, fp, fp, fp, fp, fp, ci, ci, vp, vp]),
     "vt_decoder_grads_ws_bytes": (cl, [ci, ci, ci, ci]),
     "vt_decoder_grads": (ci, [fp, vp, C.POINTER(VtMaps), fp, fp, fp, ci, ci, fp, fp, fp, fp, fp, fp, ci, C.POINTER(VtMaps), ci, ci, vp, vp]),
+    "vt_conv_dgrad_workspace_bytes": (cl, [ci, ci, ci]),
+    "vt_conv_wgrad_workspace_bytes": (cl, [ci, ci, ci, ci, ci, ci]),
+    "vt_gn_relu_backward_workspace_bytes": (cl, [ci, ci, ci, ci]),
+    "vt_conv3x3_dgrad": (ci, [fp, ci, ci, fp, ci, ci, ci, ci, ci, fp, ci, ci, vp, vp]),
+    "vt_conv1x1_dgrad": (ci, [fp, ci, ci, fp, ci, ci, ci, ci, ci, fp, ci, ci, vp, vp]),
+    "vt_conv3x3_wgrad": (ci, [fp, ci, ci, fp, ci, ci, fp, fp, fp, ci, ci, ci, ci, ci, ci, fp, ci, vp, vp]),
+    "vt_conv1x1_wgrad": (ci, [fp, ci, ci, fp, ci, ci, fp, fp, fp, ci, ci, ci, ci, ci, ci, fp, ci, vp, vp]),
+    "vt_gn_relu_backward": (ci, [fp, ci, ci, fp, ci, ci, fp, fp, fp, ci, ci, ci, ci, fp, ci, ci, fp, ci, ci, fp, fp, ci, vp, vp]),
+    "vt_conv_block_backward_workspace": (cl, [ci, ci, ci, ci, ci, ci, ci]),
+    # dy, x, raw, stats1..3 | w1..3, gamma1..3, beta1..3 | wproj, gamma4, beta4 | B, H, W, cin, c1, c2, c3 | d_x, dW1..3, (dgamma, dbeta) 1..4, dWproj | ws, accumulate, stream
+    "vt_conv_block_backward": (ci, [fp] * 6 + [fp] * 9 + [fp] * 3 + [ci] * 7 + [fp] * 13 + [vp, ci, vp]),
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
 }

@@ -355,6 +355,102 @@ class HGFilterEncoder:
         return outputs, tmpx, normx
 
 
+class TrainableConvBlock:
+    """One ConvBlock (model/net_util.py:346-396) with its parameters as fp32 device LEAVES under the reference's ``state_dict`` keys, differentiable through
+    ``ops.conv_block_train``: the forward is the fused inference forward of ``HGFilterEncoder._conv_block_fused`` bit for bit, the backward one
+    ``vt_conv_block_backward`` call (csrc/convtrain.hip).
+
+        blk = TrainableConvBlock.from_state_dict(sd, "image_filter.conv3.")
+        y = blk(x)                      # channels-last (B,Cout,H,W), carries autograd
+        y.backward(dy)                  # blk.leaves["conv1.weight"].grad, ..., x.grad
+
+    KNOWN AND NOT DONE: the forward's packed split-f16 convolution handles are rebuilt on the HOST from a leaf whenever its version counter changed (an optimiser
+    step): one device -> host -> device round trip per convolution and step.  A device-side repack is the next row."""
+    _W = ("conv1.weight", "conv2.weight", "conv3.weight")
+
+    def __init__(self, leaves: dict, device):
+        self.device = torch.device(device)
+        self.leaves = leaves
+        self.has_proj = "downsample.2.weight" in leaves
+        self._handles = {}          # key -> [handle, leaf version it was packed from]
+
+    @classmethod
+    def from_state_dict(cls, sd, prefix="", device="cuda:0"):
+        """``sd``: tensors or arrays; ``prefix`` e.g. 'image_filter.conv3.' (a leading 'module.' is stripped).  The projection's norm is read from
+        'downsample.0.*' when present (the name the reference loads last), else from 'bn4.*'; both names are written by ``state_dict()``."""
+        got = {}
+        for k, v in sd.items():
+            k = k[7:] if k.startswith("module.") else k
+            if k.startswith(prefix):
+                got[k[len(prefix):]] = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).detach().to(device=device, dtype=torch.float32).contiguous().clone()
+        for k in cls._W + tuple(f"bn{i}.{s}" for i in (1, 2, 3) for s in ("weight", "bias")):
+            if k not in got:
+                raise KeyError(f"no ConvBlock parameter '{prefix}{k}'")
+        leaves = {k: got[k] for k in cls._W}
+        for i in (1, 2, 3):
+            leaves[f"bn{i}.weight"], leaves[f"bn{i}.bias"] = got[f"bn{i}.weight"], got[f"bn{i}.bias"]
+        n4 = "downsample.0" if "downsample.0.weight" in got else "bn4"
+        if n4 + ".weight" in got:
+            leaves["bn4.weight"], leaves["bn4.bias"] = got[n4 + ".weight"], got[n4 + ".bias"]
+        if "downsample.2.weight" in got:
+            leaves["downsample.2.weight"] = got["downsample.2.weight"]
+            if "bn4.weight" not in leaves:
+                raise KeyError(f"'{prefix}downsample.2.weight' without the projection's norm")
+        for t in leaves.values():
+            t.requires_grad_(True)
+        return cls(leaves, device)
+
+    def state_dict(self):
+        out = {k: v.detach().clone() for k, v in self.leaves.items()}
+        if self.has_proj:
+            out["downsample.0.weight"], out["downsample.0.bias"] = out["bn4.weight"].clone(), out["bn4.bias"].clone()
+        return out
+
+    def parameters(self):
+        """the leaves an optimiser updates (an identity block's bn4 is carried but not used by the reference's forward either: it never receives a gradient)"""
+        return [v for k, v in self.leaves.items() if self.has_proj or not k.startswith("bn4.")]
+
+    def tensors(self):
+        """the leaves in ``ops.CONV_BLOCK_PARAMS`` order; None for the projection's three without one"""
+        lv = self.leaves
+        proj = [lv["downsample.2.weight"], lv["bn4.weight"], lv["bn4.bias"]] if self.has_proj else [None, None, None]
+        return [lv[k] for k in self._W] + [lv[f"bn{i}.weight"] for i in (1, 2, 3)] + [lv[f"bn{i}.bias"] for i in (1, 2, 3)] + proj
+
+    def conv_handles(self, device):
+        """([3 x vt_conv3x3], vt_conv1x1 or None): the packed forward handles, rebuilt from a leaf whose version counter changed since it was packed"""
+        import ctypes as C
+        lib = L.lib()
+        out = []
+        for k in self._W + (("downsample.2.weight",) if self.has_proj else ()):
+            w = self.leaves[k]
+            ent = self._handles.get(k)
+            if ent is None or ent[1] != w._version:
+                if ent is not None:
+                    torch.cuda.synchronize(device)          # launches that read the old packing may still be queued
+                    (lib.vt_conv1x1_destroy if w.shape[2] == 1 else lib.vt_conv3x3_destroy)(ent[0])
+                cout, cin = w.shape[:2]
+                wh = np.ascontiguousarray(w.detach().cpu().numpy().reshape(cout, cin, -1), np.float32)
+                h = C.c_void_p()
+                with torch.cuda.device(device):
+                    if w.shape[2] == 1:
+                        L.check(lib.vt_conv1x1_create(C.byref(h), wh.ctypes.data, None, cout, cin, L.stream_ptr()))
+                    else:
+                        L.check(lib.vt_conv3x3_create(C.byref(h), wh.ctypes.data, cout, cin, L.stream_ptr()))
+                ent = self._handles[k] = [h, w._version]
+            out.append(ent[0])
+        return out[:3], (out[3] if self.has_proj else None)
+
+    def __del__(self):
+        try:
+            for k, (h, _) in getattr(self, "_handles", {}).items():
+                (L.lib().vt_conv1x1_destroy if k.startswith("downsample") else L.lib().vt_conv3x3_destroy)(h)
+        except Exception:
+            pass
+
+    def __call__(self, x):
+        return ops.conv_block_train(x, self)
+
+
 class SIFNetEncoder:
     """``CHORETriplane.filter`` (chore_triplane.py:60-95): image encoder on channels 0..4, the (shared or per-view) triplane encoder on
     channels 5, 6, 7; returns the eight feature maps of the query as an ``ops.FeatureMaps`` (NHWC, resident on the device)."""

@@ -842,6 +842,131 @@ def sifnet_query_train(params: DecoderParams, maps, pts, crop_center, body_cente
 
 
 # --------------------------------------------------------------------------------------------------
+# a trainable ConvBlock of the encoders (model/net_util.py:346-396)
+# --------------------------------------------------------------------------------------------------
+CONV_BLOCK_PARAMS = ("w1", "w2", "w3", "gamma1", "gamma2", "gamma3", "beta1", "beta2", "beta3", "wproj", "gamma4", "beta4")
+# flat argument order of vt_conv_block_backward (include/vistracker.h); tests/test_host_convblock.py holds it against _lib.SIGNATURES
+CONV_BLOCK_BACKWARD_ARGS = (("dy", "x", "raw", "stats1", "stats2", "stats3") + CONV_BLOCK_PARAMS + ("B", "H", "W", "cin", "c1", "c2", "c3")
+                            + ("d_x", "dW1", "dW2", "dW3", "dgamma1", "dbeta1", "dgamma2", "dbeta2", "dgamma3", "dbeta3", "dgamma4", "dbeta4", "dWproj")
+                            + ("workspace", "accumulate", "stream"))
+
+
+def conv_block_backward_raw(dy, x, raw, stats, params, want=None, out=None, accumulate=0, ws=None):
+    """one vt_conv_block_backward call.  dy / x / raw: channels-last (B,C,H,W) device tensors; stats: the three {mean, rstd} workspaces; params: dict over
+    CONV_BLOCK_PARAMS (wproj / gamma4 / beta4 None without a projection); ``want``: names of the outputs to compute (default: all that exist); ``out``: dict of
+    preallocated outputs by name (accumulate != 0 adds onto the parameter gradients in them).  -> dict name -> tensor"""
+    lib = L.lib()
+    B, cin, H, W = x.shape
+    c1, c2, c3 = (int(params[k].shape[0]) for k in ("w1", "w2", "w3"))
+    proj = params.get("wproj") is not None
+    names = ["d_x", "dW1", "dW2", "dW3", "dgamma1", "dbeta1", "dgamma2", "dbeta2", "dgamma3", "dbeta3"] + (["dgamma4", "dbeta4", "dWproj"] if proj else [])
+    like = {"d_x": x, "dW1": params["w1"], "dW2": params["w2"], "dW3": params["w3"], "dWproj": params.get("wproj")}
+    for i in "1234":
+        like["dgamma" + i] = like["dbeta" + i] = params.get("gamma" + i)
+    want = names if want is None else [n for n in names if n in want]
+    res = dict(out or {})
+    for n in want:
+        if n not in res:
+            res[n] = torch.empty_like(like[n], memory_format=torch.channels_last if n == "d_x" else torch.contiguous_format)
+    if ws is None:
+        nbytes = int(lib.vt_conv_block_backward_workspace(B, H, W, cin, c1, c2, c3))
+        if nbytes < 0:
+            raise L.VtError(f"conv_block_backward: unsupported block shape B={B} H={H} W={W} {cin}->({c1},{c2},{c3})")
+        ws = torch.empty(nbytes // 4 + 4, device=x.device)
+    ptr = lambda t: None if t is None else t.data_ptr()         # noqa: E731
+    order = ("d_x", "dW1", "dW2", "dW3", "dgamma1", "dbeta1", "dgamma2", "dbeta2", "dgamma3", "dbeta3", "dgamma4", "dbeta4", "dWproj")
+    with torch.cuda.device(x.device):
+        L.check(lib.vt_conv_block_backward(dy.data_ptr(), x.data_ptr(), raw.data_ptr(), *[s.data_ptr() for s in stats], *[ptr(params.get(k)) for k in CONV_BLOCK_PARAMS],
+                                           B, H, W, cin, c1, c2, c3, *[ptr(res.get(n)) if n in want else None for n in order],
+                                           ws.data_ptr(), int(accumulate), L.stream_ptr()))
+    return res
+
+
+class _ConvBlockTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, blk, x, *tensors):
+        # the launches of HGFilterEncoder._conv_block_fused (encoder.py), keeping what the backward reads: x, raw = o1 | o2 and the three {mean, rstd} areas
+        lib = L.lib()
+        p = dict(zip(CONV_BLOCK_PARAMS, tensors))
+        B, Cin, H, W = x.shape
+        couts = [int(p[k].shape[0]) for k in ("w1", "w2", "w3")]
+        Ct, Cr = sum(couts), couts[0] + couts[1]
+        with torch.cuda.device(x.device):
+            h3, h1 = blk.conv_handles(x.device)
+            tiles = lib.vt_conv3x3_tiles(H, W)
+            st = getattr(x, "_vt_stats", None)          # left behind by the producer of x (a previous block): finalized on first use, as encoder._stats_of
+            if st is not None:
+                if not st[2]:
+                    L.check(lib.vt_groupnorm_finalize(st[0].data_ptr(), st[1], B, H * W, Cin, 32, 1e-5, L.stream_ptr()))
+                    st[2] = True
+                ws = st[0]
+            else:
+                ws = torch.empty(lib.vt_groupnorm_workspace_doubles(B, H * W, Cin, 32), dtype=torch.float64, device=x.device)
+                L.check(lib.vt_groupnorm_stats(x.data_ptr(), Cin, 0, B, H * W, Cin, 32, 1e-5, ws.data_ptr(), L.stream_ptr()))
+            res = x
+            if h1 is not None:
+                res = torch.empty(B, Ct, H, W, device=x.device, memory_format=torch.channels_last)
+                L.check(lib.vt_conv1x1_forward(h1, x.data_ptr(), Cin, 0, ws.data_ptr(), p["gamma4"].data_ptr(), p["beta4"].data_ptr(), 32, B, H, W,
+                                               res.data_ptr(), Ct, 0, None, Ct, 0, None, 32, L.stream_ptr()))
+            raw = torch.empty(B, Cr, H, W, device=x.device, memory_format=torch.channels_last)
+            fin = torch.empty(B, Ct, H, W, device=x.device, memory_format=torch.channels_last)
+            ws_fin = torch.empty(B * 32 + tiles * B * Ct * 2, dtype=torch.float64, device=x.device)
+            src, cstride, coff, off = x, Cin, 0, 0
+            stats = [ws]
+            for i, co in enumerate(couts):
+                last = i == 2
+                ws_out = None if last else torch.empty(B * 32 + tiles * B * co * 2, dtype=torch.float64, device=x.device)
+                L.check(lib.vt_conv3x3_forward_block_stats(h3[i], src.data_ptr(), cstride, coff, stats[-1].data_ptr(), p[f"gamma{i + 1}"].data_ptr(),
+                                                           p[f"beta{i + 1}"].data_ptr(), 32, B, H, W, None if last else raw.data_ptr(), Cr, 0 if last else off,
+                                                           res.data_ptr(), Ct, off, fin.data_ptr(), Ct, off, None if last else ws_out.data_ptr(), 32,
+                                                           ws_fin.data_ptr(), 32, L.stream_ptr()))
+                if not last:
+                    L.check(lib.vt_groupnorm_finalize(ws_out.data_ptr(), tiles, B, H * W, co, 32, 1e-5, L.stream_ptr()))
+                    stats.append(ws_out)
+                src, cstride, coff = raw, Cr, off
+                off += co
+        ctx.save_for_backward(x, raw, *stats, *[t for t in tensors if t is not None])
+        ctx.present = [t is not None for t in tensors]
+        ctx.mark_non_differentiable(ws_fin)
+        return fin, ws_fin
+
+    @staticmethod
+    def backward(ctx, dy, _):
+        sv = ctx.saved_tensors
+        x, raw, stats = sv[0], sv[1], sv[2:5]
+        it = iter(sv[5:])
+        p = {k: (next(it) if have else None) for k, have in zip(CONV_BLOCK_PARAMS, ctx.present)}
+        need = dict(zip(("d_x",) + CONV_BLOCK_PARAMS, ctx.needs_input_grad[1:]))
+        gname = {"d_x": "d_x", "w1": "dW1", "w2": "dW2", "w3": "dW3", "wproj": "dWproj"}
+        for i in "1234":
+            gname["gamma" + i], gname["beta" + i] = "dgamma" + i, "dbeta" + i
+        want = [gname[k] for k, n in need.items() if n and (k == "d_x" or p[k] is not None)]
+        dy = dy.float().contiguous(memory_format=torch.channels_last)
+        g = conv_block_backward_raw(dy, x, raw, stats, p, want=want)
+        return (None, g.get("d_x"), *[g.get(gname[k]) if need[k] and p[k] is not None else None for k in CONV_BLOCK_PARAMS])
+
+
+def conv_block_train(x, params):
+    """A ConvBlock (model/net_util.py:346-396) that a torch graph can contain.  ``x``: (B,Cin,H,W) device tensor (kept channels-last); ``params``: an
+    ``encoder.TrainableConvBlock`` (its leaves ``tensors()`` in CONV_BLOCK_PARAMS order and the packed forward handles ``conv_handles(device)``).  Forward:
+    exactly the fused inference forward (the launches of ``HGFilterEncoder._conv_block_fused``); backward: one ``vt_conv_block_backward`` call, a gradient for
+    every input that requires one.  The result carries the GroupNorm partial sums of itself for a block that reads it next, as the inference path does."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
+        raise L.VtError("conv_block_train: x must be a (B,C,H,W) device tensor; there is no CPU path")
+    B, Cin, H, W = x.shape
+    tensors = params.tensors()
+    couts = [int(tensors[i].shape[0]) for i in range(3)]
+    if int(L.lib().vt_conv_block_backward_workspace(B, H, W, Cin, *couts)) < 0 or int(tensors[0].shape[1]) != Cin or (tensors[9] is None) != (Cin == sum(couts)):
+        raise L.VtError(f"conv_block_train: block {Cin}->{couts} at {H}x{W} is not served (H % 8 == 0, W % 16 == 0, widths in {{32, 64, 128}}, Cin % 32 == 0 up to 256)")
+    xc = x if x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last) else x.float().contiguous(memory_format=torch.channels_last)
+    if xc is not x and hasattr(x, "_vt_stats"):
+        xc._vt_stats = x._vt_stats
+    fin, ws_fin = _ConvBlockTrainFn.apply(params, xc, *tensors)
+    fin._vt_stats = [ws_fin, int(L.lib().vt_conv3x3_tiles(H, W)), False]
+    return fin
+
+
+# --------------------------------------------------------------------------------------------------
 # silhouette
 # --------------------------------------------------------------------------------------------------
 class _SilFn(torch.autograd.Function):
