@@ -879,6 +879,11 @@ def test_conv3x3_split_f16_vs_float64(hip, cin, cout):
     got = npy(out)
     assert np.abs(got[..., coff:coff + cout] - ref).max() < 2e-6 * np.abs(ref).max()
     assert (got[..., :coff] == 7.0).all() and (got[..., coff + cout:] == 7.0).all()                     # nothing outside the channel slice is touched
+    # ... and per output channel / per element, the gates of tests/test_gpu_encoder_kernels.py (8 x the error of the number format's emulation; the format's worst case)
+    import encoder_model as EM
+    xh = x.permute(0, 2, 3, 1).numpy(); r = EM.conv3x3(xh, w.numpy()); e_emu = EM.per_channel_error(EM.emu_conv(xh, w.numpy())["out"], r["out"])
+    assert (EM.per_channel_error(got[..., coff:coff + cout], r["out"]) <= 8 * e_emu).all()
+    assert (np.abs(got[..., coff:coff + cout] - r["out"]) <= EM.conv_backstop(r)).all()
     xn[0, 3, 5, 7] = 5000.0                                                                            # 5000 * 2^4 > 65504
     L.check(L.lib().vt_conv3x3_forward(h, L.dptr(xn), B, H, W, L.dptr(out), ctot, coff, L.stream_ptr()))
     assert torch.isnan(out[0, 0:8, 0:16, coff:coff + cout]).all() and torch.isfinite(out[1]).all()       # the tiles that saw it are poisoned, others fine
@@ -997,6 +1002,11 @@ def test_conv1x1_vs_float64(hip, cin, cout):
     got = npy(out)
     assert np.abs(got[..., 8:8 + cout] - ref).max() < 3e-6 * sc, np.abs(got[..., 8:8 + cout] - ref).max() / sc
     assert (got[..., :8] == 7.0).all() and (got[..., 8 + cout:] == 7.0).all()
+    import encoder_model as EM                                                     # per output channel / per element (tests/test_gpu_encoder_kernels.py)
+    xh = xin.permute(0, 2, 3, 1).numpy(); r = EM.conv1x1(xh, w.numpy()[:, :, None, None], bias.numpy())
+    e_emu = EM.per_channel_error(EM.emu_conv(xh, w.numpy()[:, :, None, None], bias.numpy())["out"], r["out"])
+    assert (EM.per_channel_error(got[..., 8:8 + cout], r["out"]) <= 8 * e_emu).all()
+    assert (np.abs(got[..., 8:8 + cout] - r["out"]) <= EM.conv_backstop(r)).all()
     st = ws2[:B * groups].view(torch.float32).view(B, groups, 2).cpu().numpy().astype(np.float64)
     o = ref.reshape(B, H * W, groups, cout // groups)
     mean = o.mean((1, 3)); rstd = 1 / np.sqrt(o.var((1, 3)) + 1e-5)
