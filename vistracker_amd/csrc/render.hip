@@ -67,9 +67,10 @@ __device__ __forceinline__ float rnd_depth(const float (&fc)[9], float den, floa
             if (zp_ > RND_NEAR * 1.001f && zp_ < RND_FAR * 0.999f) return zp_;
         }
     }
-    float w0 = n0 / den;
-    float w1 = n1 / den;
-    float w2 = n2 / den;
+    // (the coefficients are divided by den first, as neural_renderer and sil.hip's sil_vote do: the two rasterisers stay bit-identical)
+    float w0 = (fc[4] - fc[7]) / den * xp + (fc[6] - fc[3]) / den * yp + (fc[3] * fc[7] - fc[6] * fc[4]) / den;
+    float w1 = (fc[7] - fc[1]) / den * xp + (fc[0] - fc[6]) / den * yp + (fc[6] * fc[1] - fc[0] * fc[7]) / den;
+    float w2 = (fc[1] - fc[4]) / den * xp + (fc[3] - fc[0]) / den * yp + (fc[0] * fc[4] - fc[3] * fc[1]) / den;
     w0 = fminf(fmaxf(w0, 0.f), 1.f); w1 = fminf(fmaxf(w1, 0.f), 1.f); w2 = fminf(fmaxf(w2, 0.f), 1.f);
     const float ws = w0 + w1 + w2;
     const float zp = 1.0f / (w0 / ws / fc[2] + w1 / ws / fc[5] + w2 / ws / fc[8]);

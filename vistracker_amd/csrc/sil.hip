@@ -193,9 +193,12 @@ __device__ __forceinline__ void sil_vote(const float (&fc)[9], float den, int f2
     }
 exact:
 #endif
-    float w0 = n0 / den;
-    float w1 = n1 / den;
-    float w2 = n2 / den;
+    // neural_renderer divides the nine coefficients by den FIRST and then forms the weights (oracle: inv[e] /= den; w = inv * (xp, yp, 1)).  (n / den rounds
+    // differently: two faces that meet in an edge through a pixel centre at EQUAL depth then tie or not by the last bit, and at image sizes that are no power of
+    // two the owner of such a pixel differed from the oracle's -- tests/test_gpu_sil_perpixel.py, lattice-192 / lattice-320.)
+    float w0 = (fc[4] - fc[7]) / den * xp + (fc[6] - fc[3]) / den * yp + (fc[3] * fc[7] - fc[6] * fc[4]) / den;
+    float w1 = (fc[7] - fc[1]) / den * xp + (fc[0] - fc[6]) / den * yp + (fc[6] * fc[1] - fc[0] * fc[7]) / den;
+    float w2 = (fc[1] - fc[4]) / den * xp + (fc[3] - fc[0]) / den * yp + (fc[0] * fc[4] - fc[3] * fc[1]) / den;
     w0 = fminf(fmaxf(w0, 0.f), 1.f); w1 = fminf(fmaxf(w1, 0.f), 1.f); w2 = fminf(fmaxf(w2, 0.f), 1.f);
     const float ws = w0 + w1 + w2;
     const float zp = 1.0f / (w0 / ws / fc[2] + w1 / ws / fc[5] + w2 / ws / fc[8]);
@@ -750,9 +753,8 @@ extern "C" int vt_sil_step(const float *verts, int B, int NV, const int *faces, 
 extern "C" int vt_sil_forward(const float *verts, int B, int NV, const int *faces, int NF, const float *K, int size, float *image,
                               int *face_index, float *ws, void *stream)
 {
-    VT_REQUIRE(verts && faces && K && image && face_index && ws && B > 0 && NV > 0 && NF > 0 && size > 0 && size % TILE == 0 && size < 32768,
+    VT_REQUIRE(verts && faces && K && image && face_index && ws && B > 0 && NV > 0 && NF > 0 && size > 0 && size % 64 == 0 && size < 32768,
                "vt_sil_forward: bad argument (size must be a multiple of 64)");
-    VT_REQUIRE(size % 64 == 0, "vt_sil_forward: size must be a multiple of 64");
     hipStream_t st = vt_stream(stream); const int *skip = vt_skip_flag_of(st);
     const SilWs w = sil_ws(ws, B, NV, NF, size);
     hipLaunchKernelGGL(sil_project_kernel, dim3((NV + 255) / 256, B), dim3(256), 0, st, verts, K, NV, w.proj, skip);
@@ -790,7 +792,8 @@ extern "C" int vt_triplane_render(const float *verts, const float *center, int B
 extern "C" int vt_sil_backward(const float *verts, int B, int NV, const int *faces, int NF, const float *K, int size, const int *face_index,
                                const float *d_image, float eps, float *ws, float *dverts, void *stream)
 {
-    VT_REQUIRE(verts && faces && K && face_index && d_image && ws && dverts && B > 0, "vt_sil_backward: bad argument");
+    VT_REQUIRE(verts && faces && K && face_index && d_image && ws && dverts && B > 0 && NV > 0 && NF > 0 && size > 0 && size % 64 == 0 && size < 32768,
+               "vt_sil_backward: bad argument (size must be a multiple of 64)");
     hipStream_t st = vt_stream(stream); const int *skip = vt_skip_flag_of(st);
     const SilWs w = sil_ws(ws, B, NV, NF, size);
     VT_HIP(hipMemsetAsync(w.gproj, 0, sizeof(double) * (size_t)B * NV * 2, st));
