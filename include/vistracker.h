@@ -65,6 +65,22 @@ int vt_smplh_backward(const vt_smplh *h, const float *pose, const float *betas, 
                       const float *djtr, const float *v_posed, const float *ws, float *scratch,
                       float *dpose, float *dbetas, float *dtrans, void *stream);
 
+/* The same layer for a fit that keeps the hand joints fixed: SMPLHFitter's optimisers (lib_smpl/fit_SMPLH_30fps.py init_globalpose_optimizer /
+ * init_allpose_optimizer; recon/recon_fit_behave.py:430-451) hold trans, pose[:, :66] and betas only, so pose[:, 66:] (joints 22..51) is the same
+ * at every step of a fit and what SMPL_Layer.forward computes from it can be done once.
+ *   vt_smplh_prefix            pose (B,156) -> the rotations of joints 22..51 in `ws` and the blend-shape accumulators after the hand
+ *                              pose-map rows in `prefix` (vt_smplh_prefix_floats(B) floats, layout private to the library).
+ *   vt_smplh_forward_prefixed  vt_smplh_forward on top of (`ws`, `prefix`): the SAME `ws` the prefix call filled; it reads pose[:, :66] only.
+ *                              Outputs are bit-identical to vt_smplh_forward's as long as pose[:, 66:] is what the prefix call saw.
+ *   vt_smplh_backward_free     vt_smplh_backward for the first n_free_pose_cols pose columns (a multiple of 3, at most 66): dpose[:, :n], dbetas and
+ *                              dtrans are bit-identical to vt_smplh_backward's, dpose[:, n:] is NOT written.  Works behind either forward. */
+long vt_smplh_prefix_floats(int B);
+int vt_smplh_prefix(const vt_smplh *h, const float *pose, int B, float *ws, float *prefix, void *stream);
+int vt_smplh_forward_prefixed(const vt_smplh *h, const float *pose, const float *betas, const float *trans, int B, const float *prefix,
+                              float *verts, float *jtr, float *v_posed, float *ws, void *stream);
+int vt_smplh_backward_free(const vt_smplh *h, const float *pose, int B, const float *dverts, const float *djtr, const float *v_posed,
+                           const float *ws, float *scratch, int n_free_pose_cols, float *dpose, float *dbetas, float *dtrans, void *stream);
+
 /* batch_rodrigues alone: aa (n,3) -> R (n,9); and its VJP */
 int vt_rodrigues_forward(const float *aa, int n, float *R, void *stream);
 int vt_rodrigues_backward(const float *aa, int n, const float *dR, float *daa, void *stream);

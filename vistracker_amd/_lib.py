@@ -35,6 +35,10 @@ SIGNATURES = {
     "vt_smplh_bwd_scratch_floats": (cl, [ci]),
     "vt_smplh_forward": (ci, [vp, fp, fp, fp, ci, fp, fp, fp, fp, vp]),
     "vt_smplh_backward": (ci, [vp, fp, fp, ci, fp, fp, fp, fp, fp, fp, fp, fp, vp]),
+    "vt_smplh_prefix_floats": (cl, [ci]),
+    "vt_smplh_prefix": (ci, [vp, fp, ci, fp, fp, vp]),
+    "vt_smplh_forward_prefixed": (ci, [vp, fp, fp, fp, ci, fp, fp, fp, fp, fp, vp]),
+    "vt_smplh_backward_free": (ci, [vp, fp, ci, fp, fp, fp, fp, fp, ci, fp, fp, fp, vp]),
     "vt_rodrigues_forward": (ci, [fp, ci, fp, vp]),
     "vt_rodrigues_backward": (ci, [fp, ci, fp, fp, vp]),
     "vt_landmarks_create": (ci, [C.POINTER(vp), vp, vp, vp, ci, ci, vp]),

@@ -8,6 +8,15 @@
 //       Q_t   [1296 K groups][30 N tiles][64 lanes][4]   backward split-K GEMM (M = frames, N = 472 blend columns, K = vertex
 //             coordinates), stored in MFMA fragment order so that one float4 per lane feeds 4 K steps: d[pose_map | betas]
 //     both run on v_mfma_f32_16x16x4_f32.  weights -> W_jv [52][VP].  VP = 6912 = 27 * 256 (zero padded).
+//   * the fits never optimise the hand joints 22..51 (pose[:, 66:]), so both layouts put what belongs to them where it can be left out:
+//       K order of Q_kcv:  [pose-map rows of joints 22..51 (270) | 0 0 || pose-map rows of joints 1..21 (189) | betas (10) | template]
+//                          = KF_ (272, 34 pair steps) frozen rows, then 200 (25 pair steps) live rows of ONE accumulator chain.  The template is as
+//                          frozen as the hands but stays LAST: it is ~1 m against blend offsets of ~1e-3 m, and an accumulator that holds it from
+//                          the first step rounds every later step at ulp(1) (measured: v_posed 5e-7 -> 3e-6 m off the float64 model, dpose rows
+//                          past their gate); its row fills the padding of the live part and costs no step;
+//       N order of Q_t:    [pose-map columns of joints 1..21 | betas | 9 x 0 || pose-map columns of joints 22..51 | 0 0] = NT_LIVE_ (13) live tiles first.
+//     vt_smplh_prefix runs the frozen K steps once per fit, vt_smplh_forward_prefixed continues from its accumulators, vt_smplh_backward_free
+//     launches the live N tiles only; vt_smplh_forward / vt_smplh_backward run everything.
 //   * the joint regressor is folded on the host: J = J_t + J_s . beta (J = Jreg . v_shaped is linear in beta),
 //     which removes the 52x6890 reduction from every call.
 //   * forward = 2 launches (pose/chain, vertices); backward = 2 launches (vertex tile partials, per-frame
@@ -21,8 +30,22 @@
 #define NP_ VT_SMPL_NP
 #define VP_ 6912
 #define NVT_ 27 /* vertex tiles of 256 */
-#define KQ_ 472 /* 459 pose-map + 10 betas + 1 template + 2 zero rows */
+#define KQ_ 472 /* 459 pose-map + 10 betas + 1 template + 2 zero rows (order: see above) */
 #define NQ_ 480 /* padded row length of Q_t (30 N-tiles) */
+#define J_LIVE_ 22                      /* joints 0..21 move inside a fit; 22..51 (the hands) are frozen */
+#define NP_LIVE_ ((J_LIVE_ - 1) * 9)    /* 189 pose-map entries of the joints 1..21 */
+#define KF_ 272                         /* frozen K prefix of Q_kcv: 270 hand rows + two zero rows */
+#define NT_LIVE_ 13                     /* live N tiles of Q_t: 189 body pose-map columns + 10 betas (199 of 208 columns) */
+#define NQ_HAND_ (NT_LIVE_ * 16)        /* first hand pose-map column of Q_t */
+#define NP_NUM_ (J_ * 3)                 /* 156 pose columns */
+// row of Q_kcv / column of Q_t of pose-map entry p (0..458), of beta l and of the template
+__host__ __device__ constexpr int kq_of_posemap(int p) { return p < NP_LIVE_ ? KF_ + p : p - NP_LIVE_; }
+__host__ __device__ constexpr int nq_of_posemap(int p) { return p < NP_LIVE_ ? p : NQ_HAND_ + (p - NP_LIVE_); }
+#define KQ_BETA0 (KF_ + NP_LIVE_)       /* 461 */
+#define KQ_TEMPLATE (KQ_ - 1)           /* 471 */
+#define NQ_BETA0 NP_LIVE_               /* 189 */
+static_assert(KF_ % 8 == 0 && KF_ >= NP_ - NP_LIVE_ && KQ_BETA0 + NB_ <= KQ_TEMPLATE && (KQ_ - KF_) % 8 == 0, "K order of Q_kcv");
+static_assert(NQ_BETA0 + NB_ <= NQ_HAND_ && NQ_HAND_ + (NP_ - NP_LIVE_) <= NQ_, "N order of Q_t");
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
@@ -123,17 +146,33 @@ __global__ void rodrigues_bwd_kernel(const float *aa, int n, const float *dR, fl
 __global__ __launch_bounds__(64) void smplh_pose_kernel(const float *__restrict__ pose, const float *__restrict__ betas,
                                                         const float *__restrict__ trans, const float *__restrict__ J_t,
                                                         const float *__restrict__ J_s, SmplParents par,
-                                                        float *__restrict__ ws, float *__restrict__ jtr, const int *skip)
+                                                        float *__restrict__ ws, float *__restrict__ jtr, int rod_lo, int rod_hi, int chain,
+                                                        const int *skip)
 {
     VT_SKIP_RETURN(skip);
     __shared__ float sR[J_ * 9], sJ[J_ * 3], sG[J_ * 12];
     const int b = blockIdx.x, j = threadIdx.x;
     float *w = ws + (size_t)b * WS_FRAME;
+    // Rodrigues for the joints rod_lo <= j < rod_hi; the rotations of the others are the ones an earlier launch left in the workspace (vt_smplh_prefix:
+    // joints 22..51, chain = 0 -- rotations only).  One kernel for all three uses: a joint's rotation is the same instruction sequence in each.
     if (j < J_) {
-        float t[3] = {pose[(b * J_ + j) * 3], pose[(b * J_ + j) * 3 + 1], pose[(b * J_ + j) * 3 + 2]}, R[9];
-        rodrigues_fwd(t, R, nullptr);
+        float R[9];
+        if (j >= rod_lo && j < rod_hi) {
+            float t[3] = {pose[(b * J_ + j) * 3], pose[(b * J_ + j) * 3 + 1], pose[(b * J_ + j) * 3 + 2]};
+            rodrigues_fwd(t, R, nullptr);
 #pragma unroll
-        for (int e = 0; e < 9; e++) { sR[j * 9 + e] = R[e]; w[WS_R + j * 9 + e] = R[e]; }
+            for (int e = 0; e < 9; e++) w[WS_R + j * 9 + e] = R[e];
+        } else if (chain) {
+#pragma unroll
+            for (int e = 0; e < 9; e++) R[e] = w[WS_R + j * 9 + e];
+        }
+        if (chain) {
+#pragma unroll
+            for (int e = 0; e < 9; e++) sR[j * 9 + e] = R[e];
+        }
+    }
+    if (!chain) return;
+    if (j < J_) {
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             float a = J_t[j * 3 + c];
@@ -195,15 +234,21 @@ __global__ __launch_bounds__(64) void smplh_pose_kernel(const float *__restrict_
 #ifndef FWD_PF
 #define FWD_PF 6         /* pair steps of Q rows in flight in the blend-shape GEMM of smplh_verts_kernel */
 #endif
-#define AXS 516   /* LDS stride of an extended pose row [pose_map | betas | 1 | 0 0]: 516 mod 64 = 4 -> conflict-free ds_read_b64 */
+#define AXS 516   /* LDS stride of an extended pose row (the KQ_ columns in the K order of Q_kcv): 516 mod 64 = 4 -> conflict-free ds_read_b64 */
 #define SAS 628   /* LDS stride of a frame's 52 x 12 A matrices */
 #define FWD_R0 (FWD_FB * AXS > 8 * SAS ? FWD_FB * AXS : 8 * SAS)    /* floats of the time-shared region: pose rows, then 8 frames of A matrices */
+// MODE 0: the whole K range.  MODE 1 (vt_smplh_prefix): the frozen pair steps 0 .. KF_/8 - 1 only; the accumulators go to `prefix` ([workgroup][coordinate]
+// [thread] float4: the kernel's own tile order) and nothing else is written.  MODE 2 (vt_smplh_forward_prefixed): the accumulators start from `prefix` and
+// the remaining pair steps run.  A lane's accumulator sees the same MFMAs with the same operands in the same order in MODE 0 and in MODE 1 + MODE 2.
+template <int MODE>
 __global__ __launch_bounds__(256) void smplh_verts_kernel(const float *__restrict__ Q_kcv, const float *__restrict__ W_jv,
                                                           const float *__restrict__ betas, const float *__restrict__ trans,
                                                           const float *__restrict__ ws, int B,
-                                                          float *__restrict__ verts, float *__restrict__ v_posed, const float *__restrict__ W_sp, int nnz, const int *skip)
+                                                          float *__restrict__ verts, float *__restrict__ v_posed, const float *__restrict__ W_sp, int nnz,
+                                                          float *prefix, const int *skip)
 {
     VT_SKIP_RETURN(skip);
+    constexpr int K0 = MODE == 2 ? KF_ : 0, K1 = MODE == 1 ? KF_ : KQ_;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *sAx = lds;                       // [16][AXS] extended pose rows (GEMM phase) ...
     float *sA = lds;                        // ... then [8][SAS] A matrices of HALF the frames at a time (skinning phase)
@@ -212,40 +257,47 @@ __global__ __launch_bounds__(256) void smplh_verts_kernel(const float *__restric
     float *sTr = sW + (nnz > 0 ? 2 * SP_K * 64 : J_ * 64);     // [16][3]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, j = lane & 15;
     const int b0 = blockIdx.y * FWD_FB, v = blockIdx.x * 64 + wave * 16 + j;
-    // extended pose rows [pose_map | betas | 1 | 0 0] of the block's frames: a thread owns a column k and requests it for all FWD_FB frames at once (round 6: the
+    // extended pose rows of the block's frames: a thread owns a column k and requests it for all FWD_FB frames at once (round 6: the
     // element-per-thread loop was 30 rounds of one dependent load each, with a division and a modulo per element -- a third of the kernel's time)
-    for (int k = tid; k < KQ_; k += 256) {
-        const int e9 = k % 9;
-        const float sub = (k < NP_ && (e9 == 0 || e9 == 4 || e9 == 8)) ? 1.f : 0.f;
+    // (columns in the K order of Q_kcv: [hand pose map | 0 0 || body pose map | betas | 1]; a mode fills the columns K0 .. K1 - 1 it multiplies)
+    for (int k = K0 + tid; k < K1; k += 256) {
+        int p = -1, l = -1;                 // pose-map entry / beta of column k, or neither (the template's 1, a zero column)
+        if (k < NP_ - NP_LIVE_) p = NP_LIVE_ + k;
+        else if (k >= KF_ && k < KQ_BETA0) p = k - KF_;
+        else if (k >= KQ_BETA0 && k < KQ_BETA0 + NB_) l = k - KQ_BETA0;
+        const int e9 = p % 9;
+        const float sub = (p >= 0 && (e9 == 0 || e9 == 4 || e9 == 8)) ? 1.f : 0.f;
         float val[FWD_FB];
 #pragma unroll
         for (int f = 0; f < FWD_FB; f++) {
             const int b = min(b0 + f, B - 1);
-            if (k < NP_) val[f] = ws[(size_t)b * WS_FRAME + WS_R + 9 + k];
-            else if (k < NP_ + NB_) val[f] = betas[b * NB_ + (k - NP_)];
-            else val[f] = (k == NP_ + NB_) ? 1.f : 0.f;
+            if (p >= 0) val[f] = ws[(size_t)b * WS_FRAME + WS_R + 9 + p];
+            else if (l >= 0) val[f] = betas[b * NB_ + l];
+            else val[f] = (k == KQ_TEMPLATE) ? 1.f : 0.f;
         }
 #pragma unroll
         for (int f = 0; f < FWD_FB; f++) sAx[f * AXS + k] = val[f] - sub;
     }
-    if (nnz > 0) {                          // sparse LBS: sW = [nnz][64] joint indices | [nnz][64] weights of the tile
+    if (MODE == 1) {                        // the prefix needs neither weights nor translations
+    } else if (nnz > 0) {                   // sparse LBS: sW = [nnz][64] joint indices | [nnz][64] weights of the tile
         for (int i = tid; i < nnz * 64; i += 256) {
             sW[i] = W_sp[(size_t)(i >> 6) * VP_ + blockIdx.x * 64 + (i & 63)];
             sW[SP_K * 64 + i] = W_sp[(size_t)(SP_K + (i >> 6)) * VP_ + blockIdx.x * 64 + (i & 63)];
         }
     } else
         for (int i = tid; i < J_ * 64; i += 256) sW[i] = W_jv[(i >> 6) * VP_ + blockIdx.x * 64 + (i & 63)];
-    if (tid < FWD_FB * 3) { const int f = tid / 3, b = min(b0 + f, B - 1); sTr[tid] = trans[b * 3 + tid % 3]; }
+    if (MODE != 1 && tid < FWD_FB * 3) { const int f = tid / 3, b = min(b0 + f, B - 1); sTr[tid] = trans[b * 3 + tid % 3]; }
     __syncthreads();
 
     // v_posed[f][v][c] = sum_k Aext[f][k] Q[k][c][v]:  A = pose rows (LDS), B = Q rows (global, 64-B segments), 59 pair steps
     f32x4 acc[3];
+    f32x4 *pre4 = reinterpret_cast<f32x4 *>(prefix) + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3 * 256 + tid;
 #pragma unroll
-    for (int c = 0; c < 3; c++) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < 3; c++) acc[c] = MODE == 2 ? pre4[c * 256] : (f32x4){0.f, 0.f, 0.f, 0.f};
     // Round 6: the Q rows are requested FWD_PF pair steps ahead of their use (a ring of register sets, the loop fully unrolled so that the ring indices are
     // constants).  With the loads of a step issued in front of its own MFMAs (unroll 2) the loop ran one round trip to L2 / the fabric per two steps:
     // ~30 round trips = the kernel's 50 us.  Same MFMAs in the same order: bit-identical.
-    constexpr int NS = KQ_ / 8;
+    constexpr int S0 = K0 / 8, NS = K1 / 8;       // pair steps S0 .. NS - 1
     float bq[FWD_PF][2][3];
 #define FWD_LOADQ(slot_, s_)                                                                     \
     {                                                                                            \
@@ -254,18 +306,23 @@ __global__ __launch_bounds__(256) void smplh_verts_kernel(const float *__restric
             _Pragma("unroll") for (int c = 0; c < 3; c++) bq[slot_][e][c] = qk[(size_t)(e * 3 + c) * VP_]; \
     }
 #pragma unroll
-    for (int s = 0; s < FWD_PF; s++) FWD_LOADQ(s, s)
+    for (int s = 0; s < FWD_PF; s++) FWD_LOADQ(s, S0 + s)
 #pragma unroll
-    for (int s = 0; s < NS; s++) {
+    for (int s = S0; s < NS; s++) {
         const float2 av = *reinterpret_cast<const float2 *>(sAx + j * AXS + 8 * s + 2 * q);
 #pragma unroll
-        for (int c = 0; c < 3; c++) acc[c] = MFMA16(av.x, bq[s % FWD_PF][0][c], acc[c]);
+        for (int c = 0; c < 3; c++) acc[c] = MFMA16(av.x, bq[(s - S0) % FWD_PF][0][c], acc[c]);
 #pragma unroll
-        for (int c = 0; c < 3; c++) acc[c] = MFMA16(av.y, bq[s % FWD_PF][1][c], acc[c]);
-        if (s + FWD_PF < NS) FWD_LOADQ(s % FWD_PF, s + FWD_PF)
+        for (int c = 0; c < 3; c++) acc[c] = MFMA16(av.y, bq[(s - S0) % FWD_PF][1][c], acc[c]);
+        if (s + FWD_PF < NS) FWD_LOADQ((s - S0) % FWD_PF, s + FWD_PF)
         __builtin_amdgcn_sched_barrier(0);      // keeps the request where it is written: the scheduler otherwise sinks it to ~1.5 steps in front of its use
     }
 #undef FWD_LOADQ
+    if (MODE == 1) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) pre4[c * 256] = acc[c];
+        return;
+    }
     // hand v_posed over through LDS so that skinning runs with thread == vertex and a wave-uniform frame: the frame's A
     // matrices are then true LDS broadcasts and nothing is indexed dynamically in registers
     __syncthreads();                        // every wave is done with sAx: the region becomes sA
@@ -445,7 +502,7 @@ __global__ __launch_bounds__(256) void smplh_bwd_tile_kernel(const float *__rest
 #define BL_NW 1
 #endif
 #define BL_AS 132   /* LDS row stride of the staged A chunk (128 k + 4: stride = 4 mod 64 banks) */
-__global__ __launch_bounds__(256) void smplh_bwd_blend_kernel(const float *__restrict__ Q_p, const float *__restrict__ dvp_g, int B,
+__global__ __launch_bounds__(256) void smplh_bwd_blend_kernel(const float *__restrict__ Q_p, const float *__restrict__ dvp_g, int B, int ntiles,
                                                               float *__restrict__ part3, const int *skip)
 {
     VT_SKIP_RETURN(skip);
@@ -453,7 +510,10 @@ __global__ __launch_bounds__(256) void smplh_bwd_blend_kernel(const float *__res
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, j = lane & 15;
     // BL_NW = N-tiles per wave (round 6: 1, was 2): 216 workgroups of 1152 dependent-issue MFMAs per wave left the chip three quarters empty for 18 us of
     // matrix-pipe latency; 432 workgroups of 576 (the staged A chunk is read by twice as many workgroups, from L2)
+    // ntiles = N tiles the launch computes, from tile 0: all 30, or the NT_LIVE_ live ones in front (the columns behind them in part3 stay unwritten);
+    // a wave without a tile only helps to stage A
     const int ks = blockIdx.x, m0 = blockIdx.z * BL_M, nt0 = blockIdx.y * (4 * BL_NW) + wave * BL_NW;
+    const bool has_tile = nt0 < ntiles;
     f32x4 acc[6][BL_NW];
 #pragma unroll
     for (int mt = 0; mt < 6; mt++)
@@ -470,13 +530,14 @@ __global__ __launch_bounds__(256) void smplh_bwd_blend_kernel(const float *__res
             *reinterpret_cast<float4 *>(sA + row * BL_AS + c4 * 4) = v;
         }
         __syncthreads();
+        if (!has_tile) continue;            // (wave-uniform; the barriers are at the top of the chunk loop)
 #pragma unroll
         for (int g = 0; g < 8; g++) {
             const size_t kg = (size_t)ks * KG_SLAB + c * 8 + g;
             float bq[BL_NW][4];
 #pragma unroll
             for (int n = 0; n < BL_NW; n++) {
-                const float4 fq = Q4[(kg * (NQ_ / 16) + min(nt0 + n, NQ_ / 16 - 1)) * 64 + lane];
+                const float4 fq = Q4[(kg * (NQ_ / 16) + min(nt0 + n, ntiles - 1)) * 64 + lane];
                 bq[n][0] = fq.x; bq[n][1] = fq.y; bq[n][2] = fq.z; bq[n][3] = fq.w;
             }
 #pragma unroll
@@ -499,7 +560,7 @@ __global__ __launch_bounds__(256) void smplh_bwd_blend_kernel(const float *__res
                 float *dst = part3 + ((size_t)ks * B + b) * NQ_;
 #pragma unroll
                 for (int n = 0; n < BL_NW; n++)
-                    if (nt0 + n < NQ_ / 16) dst[(nt0 + n) * 16 + j] = acc[mt][n][r];
+                    if (nt0 + n < ntiles) dst[(nt0 + n) * 16 + j] = acc[mt][n][r];
             }
         }
     }
@@ -511,8 +572,8 @@ __global__ __launch_bounds__(256) void smplh_bwd_blend_kernel(const float *__res
 __global__ __launch_bounds__(256) void smplh_bwd_frame_kernel(const float *__restrict__ pose, const float *__restrict__ J_s,
                                                               SmplParents par, const float *__restrict__ ws,
                                                               const float *__restrict__ part, const float *__restrict__ part3,
-                                                              const float *__restrict__ djtr, int B, float *__restrict__ dpose, float *__restrict__ dbetas,
-                                                              float *__restrict__ dtrans, const int *skip)
+                                                              const float *__restrict__ djtr, int B, int n_free, float *__restrict__ dpose,
+                                                              float *__restrict__ dbetas, float *__restrict__ dtrans, const int *skip)
 {
     VT_SKIP_RETURN(skip);
     __shared__ float red[PT_N], red3[NQ_];
@@ -530,7 +591,9 @@ __global__ __launch_bounds__(256) void smplh_bwd_frame_kernel(const float *__res
         for (int t = 0; t < NVT_; t++) s += part[((size_t)t * B + b) * PT_N + i];
         red[i] = s;
     }
-    for (int i = tid; i < NQ_; i += 256) {
+    // n_free < 156 (vt_smplh_backward_free): part3 holds the live columns only, dpose[:, n_free:] is not written (joints from n_free / 3 on are frozen)
+    const int ncol = n_free < NP_NUM_ ? NQ_HAND_ : NQ_, jfree = n_free / 3;
+    for (int i = tid; i < ncol; i += 256) {
         float s = 0.f;
 #pragma unroll 9
         for (int t = 0; t < NKS_; t++) s += part3[((size_t)t * B + b) * NQ_ + i];
@@ -586,16 +649,16 @@ __global__ __launch_bounds__(256) void smplh_bwd_frame_kernel(const float *__res
     }
     if (tid < 3) { for (int c = 0; c < 3; c++) sdR[3 * tid + c] += sdG[tid * 4 + c]; sdJ[tid] += sdG[tid * 4 + 3]; }
     __syncthreads();
-    if (tid < J_) {
+    if (tid < jfree) {
         const int j = tid;
         float g[9], t[3] = {pose[(b * J_ + j) * 3], pose[(b * J_ + j) * 3 + 1], pose[(b * J_ + j) * 3 + 2]}, d[3];
 #pragma unroll
-        for (int e = 0; e < 9; e++) g[e] = sdR[9 * j + e] + (j >= 1 ? red3[(j - 1) * 9 + e] : 0.f);
+        for (int e = 0; e < 9; e++) g[e] = sdR[9 * j + e] + (j >= 1 ? red3[nq_of_posemap((j - 1) * 9 + e)] : 0.f);
         rodrigues_bwd(t, g, d);
         dpose[(b * J_ + j) * 3] = d[0]; dpose[(b * J_ + j) * 3 + 1] = d[1]; dpose[(b * J_ + j) * 3 + 2] = d[2];
     } else if (tid >= 64 && tid < 64 + NB_) {
         const int l = tid - 64;
-        float s = red3[NP_ + l];
+        float s = red3[NQ_BETA0 + l];
         for (int i = 0; i < J_ * 3; i++) s += J_s[i * NB_ + l] * sdJ[i];
         dbetas[b * NB_ + l] = s;
     } else if (tid >= 128 && tid < 131) {
@@ -637,10 +700,13 @@ extern "C" int vt_smplh_create(vt_smplh **out, const float *v_template, const fl
         for (int k = 0; k < NP_ + NB_ + 1; k++) {
             const float val = k < NP_ ? posedirs[((size_t)v * 3 + c) * NP_ + k]
                             : (k < NP_ + NB_ ? shapedirs[((size_t)v * 3 + c) * NB_ + (k - NP_)] : v_template[v * 3 + c]);
-            Q_kcv[(size_t)(k * 3 + c) * VP_ + v] = val;
-            {   // fragment-ordered Q for the backward GEMM: [k group][N tile][lane = (q, j)][step s] <- row 16g + 4q + s, column 16nt + j
+            // forward: frozen rows (hand pose map) first, the template last; backward: live columns (body pose map, betas) first -- see the head of this file
+            const int kq = k < NP_ ? kq_of_posemap(k) : (k < NP_ + NB_ ? KQ_BETA0 + (k - NP_) : KQ_TEMPLATE);
+            Q_kcv[(size_t)(kq * 3 + c) * VP_ + v] = val;
+            if (k < NP_ + NB_) {   // fragment-ordered Q for the backward GEMM: [k group][N tile][lane = (q, j)][step s] <- row 16g + 4q + s, column 16nt + j
+                const int nq = k < NP_ ? nq_of_posemap(k) : NQ_BETA0 + (k - NP_);
                 const size_t kr = (size_t)v * 3 + c, g = kr >> 4, qq = (kr & 15) >> 2, ss = kr & 3;
-                Q_t[((g * (NQ_ / 16) + (k >> 4)) * 64 + qq * 16 + (k & 15)) * 4 + ss] = val;   // column 469 (template) is never used
+                Q_t[((g * (NQ_ / 16) + (nq >> 4)) * 64 + qq * 16 + (nq & 15)) * 4 + ss] = val;   // (no template column: nothing differentiates by it)
             }
         }
     }
@@ -696,17 +762,69 @@ extern "C" long vt_smplh_bwd_scratch_floats(int B) { return (long)NVT_ * B * PT_
 
 #define BWD_FB 6      /* frames per workgroup of the backward tile kernel: 27 x 16 = 432 workgroups at B = 96 fill the 512 slots better than 27 x 12 (8 frames): 141 -> 131 us */
 
+extern "C" long vt_smplh_prefix_floats(int B) { return (long)((B + FWD_FB - 1) / FWD_FB) * (VP_ / 64) * 3 * 256 * 4; }
+
+#define FWD_LDS_FLOATS(w_) (FWD_R0 + FWD_FB * 64 * 3 + (w_) + FWD_FB * 3)
+// launches of the forward: mode 0 = everything, 1 = the frozen part (hand rotations -> ws, frozen K steps -> prefix), 2 = the rest on top of (ws, prefix)
+static int smplh_forward_launch(int mode, const vt_smplh *h, const float *pose, const float *betas, const float *trans, int B, float *verts, float *jtr,
+                                float *v_posed, float *ws, float *prefix, hipStream_t st)
+{
+    const int *skip = mode == 1 ? nullptr : vt_skip_flag_of(st);     // the prefix is built before a fit's first step and is never skipped
+    hipLaunchKernelGGL(smplh_pose_kernel, dim3(B), dim3(64), 0, st, pose, betas, trans, h->J_t, h->J_s, h->par, ws, jtr, mode == 1 ? J_LIVE_ : 0,
+                       mode == 2 ? J_LIVE_ : J_, mode == 1 ? 0 : 1, skip);
+    VT_LAUNCH_CHECK();
+    const size_t lds_f = sizeof(float) * FWD_LDS_FLOATS(h->nnz > 0 ? 2 * SP_K * 64 : J_ * 64), lds_max = sizeof(float) * FWD_LDS_FLOATS(J_ * 64);
+    const dim3 grid(VP_ / 64, (B + FWD_FB - 1) / FWD_FB);
+    if (mode == 0) {
+        VT_LDS_LIMIT(smplh_verts_kernel<0>, lds_max);     // the limit is set once per device: the dense-weights size
+        hipLaunchKernelGGL(smplh_verts_kernel<0>, grid, dim3(256), lds_f, st, h->Q_kcv, h->W_jv, betas, trans, ws, B, verts, v_posed, h->W_sp, h->nnz, prefix, skip);
+    } else if (mode == 1) {
+        VT_LDS_LIMIT(smplh_verts_kernel<1>, sizeof(float) * FWD_R0);
+        hipLaunchKernelGGL(smplh_verts_kernel<1>, grid, dim3(256), sizeof(float) * FWD_R0, st, h->Q_kcv, h->W_jv, betas, trans, ws, B, verts, v_posed, h->W_sp,
+                           h->nnz, prefix, skip);
+    } else {
+        VT_LDS_LIMIT(smplh_verts_kernel<2>, lds_max);
+        hipLaunchKernelGGL(smplh_verts_kernel<2>, grid, dim3(256), lds_f, st, h->Q_kcv, h->W_jv, betas, trans, ws, B, verts, v_posed, h->W_sp, h->nnz, prefix, skip);
+    }
+    VT_LAUNCH_CHECK();
+    return VT_OK;
+}
+
 extern "C" int vt_smplh_forward(const vt_smplh *h, const float *pose, const float *betas, const float *trans, int B,
                                 float *verts, float *jtr, float *v_posed, float *ws, void *stream)
 {
     VT_REQUIRE(h && pose && betas && trans && verts && v_posed && ws && B > 0, "vt_smplh_forward: null argument or B <= 0");
-    hipStream_t st = vt_stream(stream); const int *skip = vt_skip_flag_of(st);
-    hipLaunchKernelGGL(smplh_pose_kernel, dim3(B), dim3(64), 0, st, pose, betas, trans, h->J_t, h->J_s, h->par, ws, jtr, skip);
+    return smplh_forward_launch(0, h, pose, betas, trans, B, verts, jtr, v_posed, ws, nullptr, vt_stream(stream));
+}
+
+extern "C" int vt_smplh_prefix(const vt_smplh *h, const float *pose, int B, float *ws, float *prefix, void *stream)
+{
+    VT_REQUIRE(h && pose && ws && prefix && B > 0, "vt_smplh_prefix: null argument or B <= 0");
+    return smplh_forward_launch(1, h, pose, nullptr, nullptr, B, nullptr, nullptr, nullptr, ws, prefix, vt_stream(stream));
+}
+
+extern "C" int vt_smplh_forward_prefixed(const vt_smplh *h, const float *pose, const float *betas, const float *trans, int B, const float *prefix,
+                                         float *verts, float *jtr, float *v_posed, float *ws, void *stream)
+{
+    VT_REQUIRE(h && pose && betas && trans && prefix && verts && v_posed && ws && B > 0, "vt_smplh_forward_prefixed: null argument or B <= 0");
+    return smplh_forward_launch(2, h, pose, betas, trans, B, verts, jtr, v_posed, ws, const_cast<float *>(prefix), vt_stream(stream));
+}
+
+// n_free = pose columns the caller wants the gradient of: 156 = all (every N tile of the blend GEMM), up to 66 = the live tiles only
+static int smplh_backward_launch(const vt_smplh *h, const float *pose, int B, const float *dverts, const float *djtr, const float *v_posed, const float *ws,
+                                 float *scratch, int n_free, float *dpose, float *dbetas, float *dtrans, hipStream_t st)
+{
+    const int *skip = vt_skip_flag_of(st);
+    const size_t lds = sizeof(float) * (256 * 13 + BWD_FB * 624);
+    float *dvp_g = scratch + (size_t)NVT_ * B * PT_N, *part3 = dvp_g + (size_t)B * KTOT_;
+    const int ntiles = n_free < NP_NUM_ ? NT_LIVE_ : NQ_ / 16;
+    VT_LDS_LIMIT(smplh_bwd_tile_kernel<BWD_FB>, lds);
+    hipLaunchKernelGGL(smplh_bwd_tile_kernel<BWD_FB>, dim3(NVT_, (B + BWD_FB - 1) / BWD_FB), dim3(256), lds, st, h->W_v64, ws, v_posed, dverts, B, scratch, dvp_g, skip);
     VT_LAUNCH_CHECK();
-    const size_t lds_f = sizeof(float) * (FWD_R0 + FWD_FB * 64 * 3 + (h->nnz > 0 ? 2 * SP_K * 64 : J_ * 64) + FWD_FB * 3);
-    VT_LDS_LIMIT(smplh_verts_kernel, sizeof(float) * (FWD_R0 + FWD_FB * 64 * 3 + J_ * 64 + FWD_FB * 3));     // the limit is set once per device: the dense-weights size
-    hipLaunchKernelGGL(smplh_verts_kernel, dim3(VP_ / 64, (B + FWD_FB - 1) / FWD_FB), dim3(256), lds_f, st, h->Q_kcv, h->W_jv, betas, trans, ws, B,
-                       verts, v_posed, h->W_sp, h->nnz, skip);
+    hipLaunchKernelGGL(smplh_bwd_blend_kernel, dim3(NKS_, (ntiles + 4 * BL_NW - 1) / (4 * BL_NW), (B + BL_M - 1) / BL_M), dim3(256), 0, st, h->Q_t, dvp_g, B, ntiles,
+                       part3, skip);
+    VT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(smplh_bwd_frame_kernel, dim3(B), dim3(256), 0, st, pose, h->J_s, h->par, ws, scratch, part3, djtr, B, n_free, dpose, dbetas, dtrans, skip);
     VT_LAUNCH_CHECK();
     return VT_OK;
 }
@@ -717,17 +835,17 @@ extern "C" int vt_smplh_backward(const vt_smplh *h, const float *pose, const flo
 {
     (void)betas;
     VT_REQUIRE(h && pose && dverts && v_posed && ws && scratch && dpose && dbetas && dtrans && B > 0, "vt_smplh_backward: null argument or B <= 0");
-    hipStream_t st = vt_stream(stream); const int *skip = vt_skip_flag_of(st);
-    const size_t lds = sizeof(float) * (256 * 13 + BWD_FB * 624);
-    float *dvp_g = scratch + (size_t)NVT_ * B * PT_N, *part3 = dvp_g + (size_t)B * KTOT_;
-    VT_LDS_LIMIT(smplh_bwd_tile_kernel<BWD_FB>, lds);
-    hipLaunchKernelGGL(smplh_bwd_tile_kernel<BWD_FB>, dim3(NVT_, (B + BWD_FB - 1) / BWD_FB), dim3(256), lds, st, h->W_v64, ws, v_posed, dverts, B, scratch, dvp_g, skip);
-    VT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(smplh_bwd_blend_kernel, dim3(NKS_, (NQ_ / 16 + 4 * BL_NW - 1) / (4 * BL_NW), (B + BL_M - 1) / BL_M), dim3(256), 0, st, h->Q_t, dvp_g, B, part3, skip);
-    VT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(smplh_bwd_frame_kernel, dim3(B), dim3(256), 0, st, pose, h->J_s, h->par, ws, scratch, part3, djtr, B, dpose, dbetas, dtrans, skip);
-    VT_LAUNCH_CHECK();
-    return VT_OK;
+    return smplh_backward_launch(h, pose, B, dverts, djtr, v_posed, ws, scratch, NP_NUM_, dpose, dbetas, dtrans, vt_stream(stream));
+}
+
+extern "C" int vt_smplh_backward_free(const vt_smplh *h, const float *pose, int B, const float *dverts, const float *djtr, const float *v_posed,
+                                      const float *ws, float *scratch, int n_free_pose_cols, float *dpose, float *dbetas, float *dtrans, void *stream)
+{
+    VT_REQUIRE(h && pose && dverts && v_posed && ws && scratch && dpose && dbetas && dtrans && B > 0, "vt_smplh_backward_free: null argument or B <= 0");
+    VT_REQUIRE(n_free_pose_cols > 0 && n_free_pose_cols <= 3 * J_LIVE_ && n_free_pose_cols % 3 == 0,
+               "vt_smplh_backward_free: n_free_pose_cols=%d must be a multiple of 3 in (0, %d] (the joints from %d on are the frozen ones of the layout)",
+               n_free_pose_cols, 3 * J_LIVE_, J_LIVE_);
+    return smplh_backward_launch(h, pose, B, dverts, djtr, v_posed, ws, scratch, n_free_pose_cols, dpose, dbetas, dtrans, vt_stream(stream));
 }
 
 extern "C" int vt_rodrigues_forward(const float *aa, int n, float *R, void *stream)

@@ -258,7 +258,7 @@ class _SmplFit(_Fit):
     buffers.  The fit adds its inputs: ``kpts``, ``temporal`` (SMPL-T); ``maps``, ``net_size``, ``crop_center``, ``body_center``, ``body_kpts``,
     ``vert_order`` (SMPL stage)."""
 
-    def __init__(self, pose, betas, trans, names, nsteps, prev_loss, prof=None):
+    def __init__(self, pose, betas, trans, names, nsteps, prev_loss, prof=None, smpl=None):
         dev = pose.device; B = self.B = pose.shape[0]
         super().__init__(dev, names, nsteps, prev_loss, prof)
         self.pose, self.betas, self.trans = pose, betas, trans
@@ -268,6 +268,15 @@ class _SmplFit(_Fit):
         self.dpose = torch.empty(B, 156, device=dev); self.dbetas = torch.empty(B, 10, device=dev); self.dtrans = torch.empty(B, 3, device=dev)
         self.vb = torch.empty(B, device=dev)
         self.pose_init = pose.clone()
+        # The hand joints' share of the SMPL-H forward, computed once (``smpl``: the SmplhHandle; None = every step runs the full layer).  INVARIANT: nothing
+        # inside a fit writes pose[:, 66:] -- no Adam group of fit_smplt / optimize_smpl reaches past column 66 (``n_free``), neither does the reference --,
+        # so ``prefix`` and the hand rotations in ``ws`` stay valid until the fit returns; they are never kept beyond it.  The restricted backward leaves
+        # dpose[:, 66:] alone: zeroed here once (the fused tail adds the pinit gradient, exactly 0 there, to columns 66..71).
+        self.prefix, self.n_free = None, 156
+        if smpl is not None:
+            self.prefix = torch.empty(_lib().vt_smplh_prefix_floats(B), device=dev); self.n_free = 66
+            _chk(_lib().vt_smplh_prefix(smpl.h, pose.data_ptr(), B, self.ws.data_ptr(), self.prefix.data_ptr(), L.stream_ptr()))
+            self.dpose.zero_()
 
     @property
     def vert_order_ptr(self):
@@ -321,6 +330,9 @@ class FitContext:
     # host look at the stop flag one outer iteration late (_StopWatch) -- the bubble a slow or contended host (8 ranks x 2 launching threads on one node)
     # would otherwise pay once per outer iteration
     device_skip = os.environ.get("VT_DEVICE_SKIP", "1") != "0"
+    # SMPL-T pre-fit and SMPL stage: the frozen hand joints' part of SMPL-H once per fit instead of once per step (_SmplFit.prefix: vt_smplh_prefix /
+    # vt_smplh_forward_prefixed / vt_smplh_backward_free); False = the full layer at every step.  Bit-identical trajectories (tests/test_gpu_smplh_frozen.py)
+    frozen_hands = True
 
     def __init__(self, smpl_model, regressors, priors, decoders=None, part_labels=None, obj_verts=None, obj_faces=None, obj_points=None,
                  cam=ops.DEFAULT_CAM, device="cuda:0"):
@@ -383,11 +395,21 @@ class FitContext:
                     self.fp32_fallbacks += 1
                 return run()
 
-    def smpl_forward(self, pose, betas, trans, verts, jtr, vposed, ws):
+    def smpl_forward(self, pose, betas, trans, verts, jtr, vposed, ws, prefix=None):
+        """``prefix``: a fit's _SmplFit.prefix (built with the same ``ws``) or None for the full layer"""
+        if prefix is not None:
+            _chk(_lib().vt_smplh_forward_prefixed(self.smpl.h, pose.data_ptr(), betas.data_ptr(), trans.data_ptr(), pose.shape[0], prefix.data_ptr(),
+                                                  verts.data_ptr(), jtr.data_ptr(), vposed.data_ptr(), ws.data_ptr(), L.stream_ptr()))
+            return
         _chk(_lib().vt_smplh_forward(self.smpl.h, pose.data_ptr(), betas.data_ptr(), trans.data_ptr(), pose.shape[0], verts.data_ptr(),
                                      jtr.data_ptr(), vposed.data_ptr(), ws.data_ptr(), L.stream_ptr()))
 
-    def smpl_backward(self, pose, betas, dverts, vposed, ws, scratch, dpose, dbetas, dtrans):
+    def smpl_backward(self, pose, betas, dverts, vposed, ws, scratch, dpose, dbetas, dtrans, n_free=156):
+        """``n_free`` < 156: the gradient of the first n_free pose columns only (dpose[:, n_free:] is left as it is)"""
+        if n_free < 156:
+            _chk(_lib().vt_smplh_backward_free(self.smpl.h, pose.data_ptr(), pose.shape[0], dverts.data_ptr(), None, vposed.data_ptr(), ws.data_ptr(),
+                                               scratch.data_ptr(), n_free, dpose.data_ptr(), dbetas.data_ptr(), dtrans.data_ptr(), L.stream_ptr()))
+            return
         _chk(_lib().vt_smplh_backward(self.smpl.h, pose.data_ptr(), betas.data_ptr(), pose.shape[0], dverts.data_ptr(), None, vposed.data_ptr(),
                                       ws.data_ptr(), scratch.data_ptr(), dpose.data_ptr(), dbetas.data_ptr(), dtrans.data_ptr(), L.stream_ptr()))
 
@@ -448,7 +470,8 @@ class FitContext:
         if weights is not None:
             table.update({k: float(v) for k, v in weights.items() if k in table})
         start, end = it_range if it_range is not None else (0, max_iter)
-        f = _SmplFit(pose, betas, trans, ["kpts", "temp", "ptemp", "pose", "pinit", "hand"], (end - start) * 10, 0.0)   # prev_loss = 0 (fit_SMPLH_kpts.py:136)
+        f = _SmplFit(pose, betas, trans, ["kpts", "temp", "ptemp", "pose", "pinit", "hand"], (end - start) * 10, 0.0,   # prev_loss = 0 (fit_SMPLH_kpts.py:136)
+                     smpl=self.smpl if self.frozen_hands else None)
         f.kpts = _as_input(kpts, pose.device)
         f.temporal = temporal and f.B >= 3
         self.hand_prior_value(pose, f.terms, "hand", f.vb)
@@ -482,7 +505,8 @@ class FitContext:
             maps.build_projection(self.net)     # rebuilt at every call: 2.5 ms per 96-frame batch, never stale (and at the maps' range level)
         total = iter_for_betas + iter_for_kpts + iter_for_pose + max_iter
         start, end = it_range if it_range is not None else (0, total)
-        f = _SmplFit(pose, betas, trans, ["df_h", "part", "pose", "pinit", "j2d", "stemp", "hand"], (end - start) * 10, 300.0, prof)  # prev_loss = 300 (recon_fit_behave.py:408)
+        f = _SmplFit(pose, betas, trans, ["df_h", "part", "pose", "pinit", "j2d", "stemp", "hand"], (end - start) * 10, 300.0, prof,  # prev_loss = 300 (recon_fit_behave.py:408)
+                     smpl=self.smpl if self.frozen_hands else None)
         f.maps, f.net_size = maps, net_size
         f.crop_center, f.body_center, f.body_kpts = _as_input(crop_center, dev), _as_input(body_center, dev), _as_input(body_kpts, dev)
         f.vert_order = self.vert_order
@@ -491,7 +515,7 @@ class FitContext:
             # little inside a batch and during the fit); a little better than the template's 3-D order because the perspective maps -- the
             # projection rows and tmpx, two thirds of the gathered bytes -- see exactly this neighbourhood structure.  Results do not depend on it.
             # Computed on the device (bit interleave + one argsort of 6890 keys): no host round trip inside the batch.
-            self.smpl_forward(pose, betas, trans, f.verts, f.jtr, f.vposed, f.ws)
+            self.smpl_forward(pose, betas, trans, f.verts, f.jtr, f.vposed, f.ws, f.prefix)
             v0 = f.verts[f.B // 2]
             f.vert_order = morton_order_device(torch.stack([v0[:, 0] / v0[:, 2], v0[:, 1] / v0[:, 2]], 1))
         self.hand_prior_value(pose, f.terms, "hand", f.vb)
@@ -531,7 +555,7 @@ class FitContext:
         dev = obj_R.device; B = obj_R.shape[0]
         _require_params(obj_R, obj_t)
         if self.use_projection and self.net.precision != "fp32" and not maps.force_fp32:
-            maps.build_projection(self.net)
+            maps.build_projection(self.net, reuse=True)     # the SMPL stage of the batch left it on these maps (same net, level, storage): kept, else built
         total = joint_iter + iter_for_obj + max_iter + iter_for_sil
         start, end = it_range if it_range is not None else (0, total)
         f = _ObjectFit(self, obj_R, obj_t, sil, (end - start) * 10, prof)
@@ -609,13 +633,13 @@ class FitContext:
         """one Adam step of the SMPL-T pre-fit (SMPLHFitter30fps.compute_loss, fit_SMPLH_30fps.py:153-200)"""
         lib = _lib(); st = L.stream_ptr(); B = f.B; pose = f.pose
         f.terms.zero(0, 5)
-        self.smpl_forward(pose, f.betas, f.trans, f.verts, f.jtr, f.vposed, f.ws)
+        self.smpl_forward(pose, f.betas, f.trans, f.verts, f.jtr, f.vposed, f.ws, f.prefix)
         _chk(lib.vt_landmarks_forward(self.b25.h, f.verts.data_ptr(), B, f.J.data_ptr(), st))
         _chk(lib.vt_kpts_loss(f.J.data_ptr(), f.kpts.data_ptr(), None, B, 25, 0, self.cam.ctypes.data, 0.0, float(w[0]), f.terms.ptr("kpts"), f.dJ.data_ptr(), st))
         _chk(lib.vt_landmarks_backward(self.b25.h, f.dJ.data_ptr(), B, f.dverts.data_ptr(), 0, st))
         if f.temporal:
             _chk(lib.vt_accel_loss(f.verts.data_ptr(), B, 6890 * 3, None, float(w[1]), f.terms.ptr("temp"), f.dverts.data_ptr(), st))
-        self.smpl_backward(pose, f.betas, f.dverts, f.vposed, f.ws, f.scratch, f.dpose, f.dbetas, f.dtrans)
+        self.smpl_backward(pose, f.betas, f.dverts, f.vposed, f.ws, f.scratch, f.dpose, f.dbetas, f.dtrans, f.n_free)
         if f.temporal:
             _chk(lib.vt_accel_loss_strided(pose.data_ptr(), B, 66, 156, self.jw66.data_ptr(), float(w[2]), f.terms.ptr("ptemp"), f.dpose.data_ptr(), st))
         self.body_prior(pose, f.dpose, float(w[3]), f.terms, "pose", f.vb)
@@ -637,7 +661,7 @@ class FitContext:
         """one Adam step of the SMPL stage as single-purpose launches (forward_smpl + the loss of recon_fit_behave.py:452-513)"""
         lib = _lib(); st = L.stream_ptr(); B = f.B; pose = f.pose
         f.terms.zero(0, 6)
-        self.smpl_forward(pose, f.betas, f.trans, f.verts, f.jtr, f.vposed, f.ws)
+        self.smpl_forward(pose, f.betas, f.trans, f.verts, f.jtr, f.vposed, f.ws, f.prefix)
         self._human_query(f, k, w)
         if phase == "kpts":
             _chk(lib.vt_landmarks_forward(self.b25.h, f.verts.data_ptr(), B, f.J.data_ptr(), st))
@@ -646,7 +670,7 @@ class FitContext:
             _chk(lib.vt_landmarks_backward(self.b25.h, f.dJ.data_ptr(), B, f.dverts.data_ptr(), 1, st))
         if B >= 4:
             _chk(lib.vt_accel_loss(f.verts.data_ptr(), B, 6890 * 3, None, float(w[5]), f.terms.ptr("stemp"), f.dverts.data_ptr(), st))
-        self.smpl_backward(pose, f.betas, f.dverts, f.vposed, f.ws, f.scratch, f.dpose, f.dbetas, f.dtrans)
+        self.smpl_backward(pose, f.betas, f.dverts, f.vposed, f.ws, f.scratch, f.dpose, f.dbetas, f.dtrans, f.n_free)
         self.body_prior(pose, f.dpose, float(w[2]), f.terms, "pose", f.vb)
         # pinit = mean_B sum (pose[:, 3:72] - pose_init)^2
         _chk(lib.vt_sqdiff_loss(pose.data_ptr() + 12, 156, f.pose_init.data_ptr() + 12, 156, B, 69, float(B), float(w[3]),
@@ -658,7 +682,7 @@ class FitContext:
     def _smpl_step_fused(self, f, phase, k, w, armed):
         """``_smpl_step`` with the keypoint chain as one launch behind the query and one tail (the tail of the previous step left the terms zeroed)"""
         lib = _lib(); st = L.stream_ptr(); B = f.B
-        self.smpl_forward(f.pose, f.betas, f.trans, f.verts, f.jtr, f.vposed, f.ws)
+        self.smpl_forward(f.pose, f.betas, f.trans, f.verts, f.jtr, f.vposed, f.ws, f.prefix)
         self._human_query(f, k, w)
         if phase == "kpts":
             # joints, 2-D keypoint term and its gradient ADDED to the query's (accumulate = 1: the float addition of vt_landmarks_backward) in one launch
@@ -666,14 +690,14 @@ class FitContext:
                                   float(w[4]), f.terms.ptr("j2d"), f.J.data_ptr(), f.dverts.data_ptr(), 1, st))
         if B >= 4:
             _chk(lib.vt_accel_loss(f.verts.data_ptr(), B, 6890 * 3, None, float(w[5]), f.terms.ptr("stemp"), f.dverts.data_ptr(), st))
-        self.smpl_backward(f.pose, f.betas, f.dverts, f.vposed, f.ws, f.scratch, f.dpose, f.dbetas, f.dtrans)
+        self.smpl_backward(f.pose, f.betas, f.dverts, f.vposed, f.ws, f.scratch, f.dpose, f.dbetas, f.dtrans, f.n_free)
         self._smpl_tail(f, k, w, armed)
 
     def _smpl_step_fused_query(self, f, phase, k, w, armed):
         """``_smpl_step_fused`` with the keypoint chain BEFORE the query and the query adding its gradient and the vertex acceleration stencil in its own
         epilogue (vt_query_human_step: 8 launches per step with the two forward and three backward SMPL-H kernels and the tail)"""
         lib = _lib(); st = L.stream_ptr(); B = f.B
-        self.smpl_forward(f.pose, f.betas, f.trans, f.verts, f.jtr, f.vposed, f.ws)
+        self.smpl_forward(f.pose, f.betas, f.trans, f.verts, f.jtr, f.vposed, f.ws, f.prefix)
         if phase == "kpts":
             _chk(lib.vt_kpts_step(self.b25.h, f.verts.data_ptr(), f.body_kpts.data_ptr(), f.crop_center.data_ptr(), B, 1, self.cam.ctypes.data, f.net_size,
                                   float(w[4]), f.terms.ptr("j2d"), f.J.data_ptr(), f.dverts.data_ptr(), 0, st))
@@ -682,7 +706,7 @@ class FitContext:
                                      self.labels.data_ptr(), f.vert_order_ptr, float(w[0]), float(w[1]), int(phase == "kpts"), float(w[5]),
                                      f.terms.ptr("stemp") if B >= 4 else None, f.dverts.data_ptr(), f.terms.ptr("df_h"), st))
         _ev_end(f.lp, "human", ev, B, k)
-        self.smpl_backward(f.pose, f.betas, f.dverts, f.vposed, f.ws, f.scratch, f.dpose, f.dbetas, f.dtrans)
+        self.smpl_backward(f.pose, f.betas, f.dverts, f.vposed, f.ws, f.scratch, f.dpose, f.dbetas, f.dtrans, f.n_free)
         self._smpl_tail(f, k, w, armed)
 
     def _smpl_tail(self, f, k, w, armed):

@@ -222,7 +222,7 @@ class FeatureMaps:
         for t, c in zip(self.t, MAP_CHANNELS):
             assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.shape[-1] == c and t.shape[1] == t.shape[2]
         self.B = self.t[0].shape[0]
-        self.proj = None
+        self.proj = None; self._proj_key = None
         self.c = L.VtMaps()
         for i, t in enumerate(self.t):
             self.c.maps[i] = t.data_ptr(); self.c.res[i] = t.shape[1]
@@ -265,21 +265,31 @@ class FeatureMaps:
             fm.c.proj = fm.proj.data_ptr(); fm.c.proj_cols = self.c.proj_cols; fm.c.proj_level = self.c.proj_level
         return fm
 
-    def build_projection(self, net):
+    def build_projection(self, net, reuse=False):
         """Hoist the im_feat part of the decoders' first layer out of the optimisation loop (vt_query_build_projection): one fp32 GEMM over
         all im_feat texels of the batch -> (B, res, res, 256) array the fused objective kernels blend instead of gathering 256 channels and
-        multiplying by W1 at every step.  Valid for these maps and the network ``net`` only; the fit loops call it once per batch."""
+        multiplying by W1 at every step.  Valid for these maps and the network ``net`` only.  The SMPL stage, the first of a batch, builds it;
+        the object stage gets the same maps and asks with ``reuse``: a projection built for the same network handle, range level, map storage
+        and stream is kept and the call returns without a launch.  The key cannot see a write INTO the maps' storage (or new weights behind the
+        same handle) between the two calls: whoever does that calls ``drop_projection()``."""
         h = net.h if hasattr(net, "h") else net.handle.h
+        key = (h.value if hasattr(h, "value") else int(h), int(self.c.act_level), tuple(t.data_ptr() for t in self.t),
+               torch.cuda.current_stream(self.t[0].device).cuda_stream)
+        if reuse and self.proj is not None and self.c.proj and self._proj_key == key:
+            return self
+        self._proj_key = None
         n = L.lib().vt_query_projection_floats(C.byref(self.c), self.B)
         self.proj = torch.empty(n, device=self.t[0].device)
         self.c.proj = None; self.c.proj_cols = 0
         L.check(L.lib().vt_query_build_projection(h, C.byref(self.c), self.B, self.proj.data_ptr(), L.stream_ptr()))
         self.c.proj = self.proj.data_ptr(); self.c.proj_cols = n // (self.B * self.t[0].shape[1] * self.t[0].shape[2])
         self.c.proj_level = self.c.act_level
+        self._proj_key = key
         return self
 
     def drop_projection(self):
-        self.proj = None; self.c.proj = None; self.c.proj_cols = 0
+        """forget the hoisted projection (also the explicit invalidation after the maps' contents or the network's weights were changed in place)"""
+        self.proj = None; self.c.proj = None; self.c.proj_cols = 0; self._proj_key = None
         return self
 
     @staticmethod
