@@ -795,6 +795,22 @@ int vt_conv_block_backward(const float *dy, const float *x, const float *raw, co
                            float *d_x, float *dW1, float *dW2, float *dW3, float *dgamma1, float *dbeta1, float *dgamma2, float *dbeta2, float *dgamma3, float *dbeta3,
                            float *dgamma4, float *dbeta4, float *dWproj, void *workspace, int accumulate, void *stream);
 
+/* ---- the backward of the two operators that join the ConvBlocks of an hourglass (resample_bwd.hip): model/HGFilters.py:26-50.  With them
+ * vt_conv_block_backward composes into the backward of a whole HourGlass (encoder.TrainableHourglass).  Tensors are NHWC fp32, pointers 16-byte aligned,
+ * C % 4 == 0.  ARITHMETIC: gathers -- one writer per element, no atomics, no workspace, nothing to initialise, a fixed order of every sum: the same inputs give
+ * the same bits on every call, and scaling d_out by a power of two scales the result by it, bit for bit.
+ *
+ * vt_avgpool2x2_backward (F.avg_pool2d(inp, 2, stride=2), HGFilters.py:32, backward; the forward is vt_avgpool2x2_stats): d_out (B,H/2,W/2,C), d_x (B,H,W,C),
+ *   d_x[b,y,x,c] = 0.25 d_out[b,y/2,x/2,c]   (exact).  H, W even.
+ * vt_upsample2x_bicubic_backward (F.interpolate(low3, scale_factor=2, mode='bicubic', align_corners=True), HGFilters.py:47, backward to low3; the forward is
+ *   vt_upsample2x_bicubic_add[_stats]): d_out (B,2h,2w,C), d_low (B,h,w,C),
+ *   d_low[b,yy,xx,c] = sum (oy,ox) Uy[oy,yy] Ux[ox,xx] d_out[b,oy,ox,c],   Uy[oy,yy] = sum of the cubic weights (A = -0.75) of the taps i = 0..3 of output row oy
+ *   with clamp(floor(sy oy) - 1 + i, 0, h - 1) == yy, sy = (h - 1) / (2h - 1) and sy oy evaluated in fp32 exactly as the forward does (a tap the border clamps
+ *   onto a row several times counts every time); Ux likewise.  Sums in fp64, rounded once.  The gradient to `skip` is d_out itself (HGFilters.py:50).
+ *   Any h, w > 0. */
+int vt_avgpool2x2_backward(const float *d_out, int B, int H, int W, int C, float *d_x, void *stream);
+int vt_upsample2x_bicubic_backward(const float *d_out, int B, int h, int w, int C, float *d_low, void *stream);
+
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two
  * workgroups of 256 threads per CU, non-trivial operands), out[1] = shader clock sustained during it (MHz: s_memtime against the 100 MHz s_memrealtime),

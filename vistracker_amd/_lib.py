@@ -173,6 +173,8 @@ SIGNATURES = {
     "vt_conv_block_backward_workspace": (cl, [ci, ci, ci, ci, ci, ci, ci]),
     # dy, x, raw, stats1..3 | w1..3, gamma1..3, beta1..3 | wproj, gamma4, beta4 | B, H, W, cin, c1, c2, c3 | d_x, dW1..3, (dgamma, dbeta) 1..4, dWproj | ws, accumulate, stream
     "vt_conv_block_backward": (ci, [fp] * 6 + [fp] * 9 + [fp] * 3 + [ci] * 7 + [fp] * 13 + [vp, ci, vp]),
+    "vt_avgpool2x2_backward": (ci, [fp, ci, ci, ci, ci, fp, vp]),
+    "vt_upsample2x_bicubic_backward": (ci, [fp, ci, ci, ci, ci, fp, vp]),
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
 }

@@ -1,6 +1,7 @@
 // encoder_ops.hip -- the element-wise passes of the image encoders (encoder.py) around the convolutions of conv.hip / stem.hip: layout conversion,
 // bicubic up-sampling, GroupNorm statistics / finalize / apply, and the pooling / up-sampling producers that leave GroupNorm partial sums behind.
 #include "common.h"
+#include "cubic.h"
 
 // NCHW -> NHWC, 32x32 LDS tile transpose per frame: src viewed as [C][HW], dst as [HW][C]
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float *__restrict__ src, int C, int HW, float *__restrict__ dst)
@@ -26,15 +27,7 @@ extern "C" int vt_nchw_to_nhwc(const float *src, int B, int C, int H, int W, flo
 // fused with the skip connection of the hourglass: out = skip + up(low)   (model/HGFilters.py:45-47).
 // thread = one output pixel x 4 channels (16-B accesses; the 16 taps of neighbouring threads hit the same cache lines).
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void cubic_w(float t, float *w)
-{
-    const float A = -0.75f;
-    const float x0 = t + 1.f, x1 = t, x2 = 1.f - t, x3 = 2.f - t;
-    w[0] = ((A * x0 - 5.f * A) * x0 + 8.f * A) * x0 - 4.f * A;
-    w[1] = ((A + 2.f) * x1 - (A + 3.f)) * x1 * x1 + 1.f;
-    w[2] = ((A + 2.f) * x2 - (A + 3.f)) * x2 * x2 + 1.f;
-    w[3] = ((A * x3 - 5.f * A) * x3 + 8.f * A) * x3 - 4.f * A;
-}
+// cubic_w: cubic.h (shared with the transpose, resample_bwd.hip)
 __global__ __launch_bounds__(256) void upsample2x_bicubic_add_kernel(const float *__restrict__ low, const float *__restrict__ skip, int B, int h, int w, int C,
                                                                      float *__restrict__ out)
 {

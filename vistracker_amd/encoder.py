@@ -451,6 +451,59 @@ class TrainableConvBlock:
         return ops.conv_block_train(x, self)
 
 
+class TrainableHourglass:
+    """One ``HourGlass(1, depth, features, norm='group')`` (model/HGFilters.py:4-53) that trains: a ``TrainableConvBlock`` per reference module in ``.blocks``
+    (keys 'b1_n', 'b2_n', 'b3_n' for n = depth .. 1 and 'b2_plus_1', the reference's ``state_dict`` names), joined by ``ops.avgpool2x2_train`` and
+    ``ops.upsample2x_bicubic_add_train``.  The forward is the recursion of ``HGFilterEncoder._hourglass`` bit for bit; the backward is one
+    ``vt_conv_block_backward`` call per block, one ``vt_avgpool2x2_backward`` and one ``vt_upsample2x_bicubic_backward`` per level.
+
+        hg = TrainableHourglass.from_state_dict(sd, "image_filter.m0.", depth=2)
+        y = hg(x)                       # channels-last (B,features,H,W), carries autograd
+        y.backward(dy)                  # hg.blocks["b2_plus_1"].leaves["conv1.weight"].grad, ..., x.grad
+
+    A shape that a block does not serve raises that block's own error (H % 8 == 0 and W % 16 == 0 must still hold at the innermost level).
+
+    KNOWN AND NOT DONE: every block rebuilds its packed forward handles on the HOST after an optimiser step (see ``TrainableConvBlock``): an hourglass of depth 2
+    makes 21 host round trips per step (7 blocks x 3 convolutions) until the device-side repack lands."""
+
+    def __init__(self, blocks: dict, depth: int, device):
+        self.device = torch.device(device)
+        self.depth = int(depth)
+        self.blocks = blocks
+
+    @staticmethod
+    def block_names(depth):
+        """the reference's module names in registration order (HGFilters.py:14-24)"""
+        names = []
+        for n in range(depth, 0, -1):
+            names += [f"b1_{n}", f"b2_{n}"]
+        names.append("b2_plus_1")
+        return names + [f"b3_{n}" for n in range(1, depth + 1)]
+
+    @classmethod
+    def from_state_dict(cls, sd, prefix="", depth=2, device="cuda:0"):
+        """``sd``: tensors or arrays; ``prefix`` e.g. 'image_filter.m0.' (a leading 'module.' is stripped)"""
+        if depth < 1:
+            raise ValueError("depth >= 1")
+        return cls({n: TrainableConvBlock.from_state_dict(sd, f"{prefix}{n}.", device=device) for n in cls.block_names(depth)}, depth, device)
+
+    def state_dict(self):
+        return {f"{n}.{k}": v for n, blk in self.blocks.items() for k, v in blk.state_dict().items()}
+
+    def parameters(self):
+        return [p for blk in self.blocks.values() for p in blk.parameters()]
+
+    def _level(self, n, x):
+        up1 = self.blocks[f"b1_{n}"](x)
+        low = self.blocks[f"b2_{n}"](ops.avgpool2x2_train(x))
+        low = self._level(n - 1, low) if n > 1 else self.blocks["b2_plus_1"](low)
+        low = self.blocks[f"b3_{n}"](low)
+        return ops.upsample2x_bicubic_add_train(low, up1)
+
+    def __call__(self, x):
+        return self._level(self.depth, x)
+
+
 class SIFNetEncoder:
     """``CHORETriplane.filter`` (chore_triplane.py:60-95): image encoder on channels 0..4, the (shared or per-view) triplane encoder on
     channels 5, 6, 7; returns the eight feature maps of the query as an ``ops.FeatureMaps`` (NHWC, resident on the device)."""

@@ -977,6 +977,102 @@ def conv_block_train(x, params):
 
 
 # --------------------------------------------------------------------------------------------------
+# the two operators that join the ConvBlocks of an hourglass (model/HGFilters.py:26-50), trainable
+# --------------------------------------------------------------------------------------------------
+def _resample_arg(what, t):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dim() == 4):
+        raise L.VtError(f"{what}: needs a (B,C,H,W) device tensor; there is no CPU path")
+    return t if t.dtype == torch.float32 and t.is_contiguous(memory_format=torch.channels_last) else t.float().contiguous(memory_format=torch.channels_last)
+
+
+def avgpool2x2_backward(d_out):
+    """one vt_avgpool2x2_backward call: d_out (B,C,H/2,W/2) channels-last -> d_x (B,C,H,W) = 0.25 d_out at [y/2, x/2] (F.avg_pool2d(x, 2, stride=2) backward)"""
+    d = _resample_arg("avgpool2x2_backward", d_out)
+    B, C, h, w = d.shape
+    d_x = torch.empty(B, C, 2 * h, 2 * w, device=d.device, memory_format=torch.channels_last)
+    with torch.cuda.device(d.device):
+        L.check(L.lib().vt_avgpool2x2_backward(d.data_ptr(), B, 2 * h, 2 * w, C, d_x.data_ptr(), L.stream_ptr()))
+    return d_x
+
+
+def upsample2x_bicubic_backward(d_out):
+    """one vt_upsample2x_bicubic_backward call: d_out (B,C,2h,2w) channels-last -> d_low (B,C,h,w), the transpose of the forward's bicubic x2 operator
+    (F.interpolate(low, scale_factor=2, mode='bicubic', align_corners=True) backward)"""
+    d = _resample_arg("upsample2x_bicubic_backward", d_out)
+    B, C, H, W = d.shape
+    if H % 2 or W % 2:
+        raise L.VtError(f"upsample2x_bicubic_backward: d_out is {H}x{W}, not twice a size")
+    d_low = torch.empty(B, C, H // 2, W // 2, device=d.device, memory_format=torch.channels_last)
+    with torch.cuda.device(d.device):
+        L.check(L.lib().vt_upsample2x_bicubic_backward(d.data_ptr(), B, H // 2, W // 2, C, d_low.data_ptr(), L.stream_ptr()))
+    return d_low
+
+
+class _AvgPoolTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        # the launch of encoder.avgpool2x2: the pooled tensor + the GroupNorm partial sums of it
+        B, C, H, W = x.shape
+        out = torch.empty(B, C, H // 2, W // 2, device=x.device, memory_format=torch.channels_last)
+        nblk = L.lib().vt_sweep_blocks((H // 2) * (W // 2))
+        ws = torch.empty(B * 32 + nblk * B * C * 2, dtype=torch.float64, device=x.device)
+        with torch.cuda.device(x.device):
+            L.check(L.lib().vt_avgpool2x2_stats(x.data_ptr(), B, H, W, C, out.data_ptr(), ws.data_ptr(), 32, L.stream_ptr()))
+        ctx.mark_non_differentiable(ws)
+        return out, ws
+
+    @staticmethod
+    def backward(ctx, dy, _):
+        return avgpool2x2_backward(dy)
+
+
+class _UpsampleAddTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, low, skip):
+        # the launch of encoder.upsample2x_bicubic_add: skip + up(low) + the GroupNorm partial sums of the sum
+        B, C, h, w = low.shape
+        out = torch.empty_like(skip, memory_format=torch.channels_last)
+        nblk = L.lib().vt_sweep_blocks(4 * h * w)
+        ws = torch.empty(B * 32 + nblk * B * C * 2, dtype=torch.float64, device=low.device)
+        with torch.cuda.device(low.device):
+            L.check(L.lib().vt_upsample2x_bicubic_add_stats(low.data_ptr(), skip.data_ptr(), B, h, w, C, out.data_ptr(), ws.data_ptr(), 32, L.stream_ptr()))
+        ctx.mark_non_differentiable(ws)
+        return out, ws
+
+    @staticmethod
+    def backward(ctx, dy, _):
+        # out = skip + U low: the gradient to skip is dy itself, to low U^T dy
+        return (upsample2x_bicubic_backward(dy) if ctx.needs_input_grad[0] else None), (dy if ctx.needs_input_grad[1] else None)
+
+
+def avgpool2x2_train(x):
+    """``F.avg_pool2d(x, 2, stride=2)`` that a torch graph can contain.  Forward: the inference launch (``encoder.avgpool2x2``, vt_avgpool2x2_stats) bit for
+    bit, the result carrying the GroupNorm partial sums of itself for the block that reads it next; backward: one ``vt_avgpool2x2_backward`` call."""
+    xc = _resample_arg("avgpool2x2_train", x)
+    B, C, H, W = xc.shape
+    if C % 32 or C > 1024 or H % 2 or W % 2 or H < 2 or W < 2:
+        raise L.VtError(f"avgpool2x2_train: {C} channels at {H}x{W} is not served (C % 32 == 0 up to 1024, even H and W)")
+    out, ws = _AvgPoolTrainFn.apply(xc)
+    out._vt_stats = [ws, int(L.lib().vt_sweep_blocks((H // 2) * (W // 2))), False]
+    return out
+
+
+def upsample2x_bicubic_add_train(low, skip):
+    """``skip + F.interpolate(low, scale_factor=2, mode='bicubic', align_corners=True)`` that a torch graph can contain.  Forward: the inference launch
+    (``encoder.upsample2x_bicubic_add``, vt_upsample2x_bicubic_add_stats) bit for bit, with the GroupNorm partial sums of the result attached; backward: one
+    ``vt_upsample2x_bicubic_backward`` call for ``low``, the upstream gradient itself for ``skip``."""
+    lc, sc = _resample_arg("upsample2x_bicubic_add_train", low), _resample_arg("upsample2x_bicubic_add_train", skip)
+    B, C, h, w = lc.shape
+    if tuple(sc.shape) != (B, C, 2 * h, 2 * w) or sc.device != lc.device:
+        raise L.VtError(f"upsample2x_bicubic_add_train: low {tuple(lc.shape)} and skip {tuple(sc.shape)} do not fit (skip is twice the size, same device)")
+    if C % 32 or C > 1024:
+        raise L.VtError(f"upsample2x_bicubic_add_train: {C} channels is not served (C % 32 == 0 up to 1024)")
+    out, ws = _UpsampleAddTrainFn.apply(lc, sc)
+    out._vt_stats = [ws, int(L.lib().vt_sweep_blocks(4 * h * w)), False]
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
 # silhouette
 # --------------------------------------------------------------------------------------------------
 class _SilFn(torch.autograd.Function):
