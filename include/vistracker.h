@@ -811,6 +811,46 @@ int vt_conv_block_backward(const float *dy, const float *x, const float *raw, co
 int vt_avgpool2x2_backward(const float *d_out, int B, int H, int W, int C, float *d_x, void *stream);
 int vt_upsample2x_bicubic_backward(const float *d_out, int B, int h, int w, int C, float *d_low, void *stream);
 
+/* ---- the rest of the encoder's backward (enctrain.hip; vt_gn_relu_backward_y lives with the passes it shares in convtrain.hip): the 1 x 1 tail of a stack and
+ * the stem.  With vt_conv_block_backward and the two resampling backwards they compose into the backward of a whole HGFilter (model/HGFilters.py:56-203,
+ * encoder.TrainableHGFilter).  Conventions of the ConvBlock section above: NHWC fp32 channel slices, exact fp32 products, fp64 partial sums in a fixed order rounded
+ * once, no atomics, one writer per element, nothing in a workspace needs initialising, `accumulate` != 0 adds onto parameter gradients, a power-of-two scale of the
+ * upstream gradient scales every result bit for bit, the same inputs give the same bits on every call.
+ *
+ * vt_bias_grad (the bias of nn.Conv2d: conv1 at HGFilters.py:120, conv_last / l / bl / al at HGFilters.py:146-160, backward): db[c] = sum (b, pixel)
+ *   d_out[b, pixel, c] over a channel slice.  Any HW > 0, C % 4 == 0, C <= 1024.  Per-block fp64 partials (256 pixels a block, at most 64 blocks a frame), finished
+ *   in (frame, block) order.  workspace: vt_bias_grad_workspace_bytes(B, HW, C) (-1 on bad sizes).
+ * vt_stem7x7_wgrad (conv1 = nn.Conv2d(Cin, Cout, 7, stride 2, padding 3), HGFilters.py:120, 167, backward to the weight; the forward is vt_stem7x7_forward):
+ *   dW[co,ci,ky,kx] = sum (b,oy,ox) d_y[b,oy,ox,co] x[b,2oy+ky-3,2ox+kx-3,ci], zero outside the image; d_y (B, (H-1)/2+1, (W-1)/2+1, Cout) a channel slice, x the
+ *   input slice of vt_stem7x7_forward (any stride and offset), dW (Cout, Cin, 7, 7).  Cout in {32, 64}, Cin in 1..8, any H, W > 0.  Split K over 16 x 16 output
+ *   tiles, fp32 accumulation on the f32-input MFMA within a split, the partials added in fp64 in (frame, split) order.  No data gradient (the image needs none).
+ *   workspace: vt_stem7x7_wgrad_workspace_bytes(B, H, W, cin, cout) (-1 on bad sizes).
+ * vt_gn_relu_backward_y (bn1 + ReLU of the stem, HGFilters.py:125, 167, backward): vt_gn_relu_backward with the mask m = [y > 0] READ from the forward's saved
+ *   rectified output y instead of recomputed -- vt_groupnorm_nhwc evaluates (x - mean) rstd gamma + beta, not the staging expression, and the two can differ in
+ *   sign.  Same passes, same sums, same workspace (vt_gn_relu_backward_workspace_bytes); beta is not needed.
+ * vt_stack_tail_backward (HGFilters.py:191-201 backward; forward of one stack: raw = conv_last(ll) + b, a = ReLU(bn_end(raw)), out = l(a) + b,
+ *   previous' = previous + bl(a) + b + al(out) + b): d_out (B,H,W,Co) the gradient to outputs[i], d_prev (B,H,W,C) the gradient to previous'; either may be NULL =
+ *   zero (not both).  ll, raw (B,H,W,C), out (B,H,W,Co) as the forward wrote them, stats the {mean, rstd} area of bn_end (of raw).  wcl (C,C), wl (Co,C), wbl (C,C),
+ *   wal (C,Co); wbl, wal, out may be NULL when d_prev is (the last stack has neither bl nor al).  g_out = d_out + Wal^T d_prev; d_a = Wl^T g_out + Wbl^T d_prev
+ *   (each one fp32 addition per element, operands in this order); d_raw = vt_gn_relu_backward of d_a at raw; d_ll = Wcl^T d_raw; dWal = d_prev (x) out,
+ *   dWbl = d_prev (x) a, dWl = g_out (x) a, dWcl = d_raw (x) ll with a recomputed in the staging; dbal = dbbl = sum d_prev, dbl = sum g_out, dbcl = sum d_raw.
+ *   Any output may be NULL to skip it.  The gradient to `previous` is d_prev itself.  C, Co in {64, 128, 256}, H % 8 == 0, W % 16 == 0.
+ *   workspace: vt_stack_tail_backward_workspace(B, H, W, C, Co) bytes (-1 on bad sizes). */
+long vt_bias_grad_workspace_bytes(int B, int HW, int C);
+int vt_bias_grad(const float *d_out, int do_cstride, int do_coff, int B, int HW, int C, float *db, int accumulate, void *workspace, void *stream);
+long vt_stem7x7_wgrad_workspace_bytes(int B, int H, int W, int cin, int cout);
+int vt_stem7x7_wgrad(const float *d_y, int dy_cstride, int dy_coff, const float *x, int x_cstride, int x_coff, int B, int H, int W, int cin, int cout,
+                     float *dW, int accumulate, void *workspace, void *stream);
+int vt_gn_relu_backward_y(const float *g, int g_cstride, int g_coff, const float *x_in, int x_cstride, int x_coff, const float *y, int y_cstride, int y_coff,
+                          const float *gn_stats, const float *gamma, int groups, int B, int HW, int C, const float *base, int base_cstride, int base_coff,
+                          float *d_x, int dx_cstride, int dx_coff, float *dgamma, float *dbeta, int accumulate, void *workspace, void *stream);
+long vt_stack_tail_backward_workspace(int B, int H, int W, int C, int Co);
+int vt_stack_tail_backward(const float *d_out, const float *d_prev, const float *ll, const float *raw, const float *out, const float *stats,
+                           const float *wcl, const float *gamma, const float *beta, const float *wl, const float *wbl, const float *wal,
+                           int B, int H, int W, int C, int Co,
+                           float *d_ll, float *dWcl, float *dbcl, float *dgamma, float *dbeta, float *dWl, float *dbl, float *dWbl, float *dbbl, float *dWal, float *dbal,
+                           void *workspace, int accumulate, void *stream);
+
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two
  * workgroups of 256 threads per CU, non-trivial operands), out[1] = shader clock sustained during it (MHz: s_memtime against the 100 MHz s_memrealtime),

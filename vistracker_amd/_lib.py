@@ -175,6 +175,14 @@ SIGNATURES = {
     "vt_conv_block_backward": (ci, [fp] * 6 + [fp] * 9 + [fp] * 3 + [ci] * 7 + [fp] * 13 + [vp, ci, vp]),
     "vt_avgpool2x2_backward": (ci, [fp, ci, ci, ci, ci, fp, vp]),
     "vt_upsample2x_bicubic_backward": (ci, [fp, ci, ci, ci, ci, fp, vp]),
+    "vt_bias_grad_workspace_bytes": (cl, [ci, ci, ci]),
+    "vt_bias_grad": (ci, [fp, ci, ci, ci, ci, ci, fp, ci, vp, vp]),
+    "vt_stem7x7_wgrad_workspace_bytes": (cl, [ci, ci, ci, ci, ci]),
+    "vt_stem7x7_wgrad": (ci, [fp, ci, ci, fp, ci, ci, ci, ci, ci, ci, ci, fp, ci, vp, vp]),
+    "vt_gn_relu_backward_y": (ci, [fp, ci, ci, fp, ci, ci, fp, ci, ci, fp, fp, ci, ci, ci, ci, fp, ci, ci, fp, ci, ci, fp, fp, ci, vp, vp]),
+    "vt_stack_tail_backward_workspace": (cl, [ci, ci, ci, ci, ci]),
+    # d_out, d_prev, ll, raw, out, stats | wcl, gamma, beta, wl, wbl, wal | B, H, W, C, Co | d_ll, dWcl, dbcl, dgamma, dbeta, dWl, dbl, dWbl, dbbl, dWal, dbal | ws, accumulate, stream
+    "vt_stack_tail_backward": (ci, [fp] * 6 + [fp] * 6 + [ci] * 5 + [fp] * 11 + [vp, ci, vp]),
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
 }

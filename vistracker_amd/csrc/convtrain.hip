@@ -232,9 +232,11 @@ __device__ __forceinline__ bool gnb_mask(float x, float2 st, float gm, float bt)
     const float a_ = st.y * gm;
     return __builtin_fmaf(x, a_, bt - st.x * a_) > 0.f;
 }
+// YM: the mask is read from the forward's saved rectified output, m = [y > 0] (vt_gn_relu_backward_y: a forward whose expression is not the staging one)
+template <bool YM>
 __global__ __launch_bounds__(256) void gnb_reduce_kernel(const float *__restrict__ g, int g_cs, const float *__restrict__ x, int x_cs, const float2 *__restrict__ stats,
                                                          const float *__restrict__ gamma, const float *__restrict__ beta, int groups, int HW, int C, int rows_per_block,
-                                                         double *__restrict__ part)
+                                                         double *__restrict__ part, const float *__restrict__ y, int y_cs)
 {
     const int C4 = C >> 2, b = blockIdx.y, c4 = threadIdx.x % C4, slot = threadIdx.x / C4, nslot = 256 / C4, cg = C / groups;
     const int p0 = blockIdx.x * rows_per_block, p1 = min(HW, p0 + rows_per_block);
@@ -247,9 +249,11 @@ __global__ __launch_bounds__(256) void gnb_reduce_kernel(const float *__restrict
             const float4 gv = *reinterpret_cast<const float4 *>(g + ((size_t)b * HW + p) * g_cs + 4 * c4);
             const float4 xv = *reinterpret_cast<const float4 *>(x + ((size_t)b * HW + p) * x_cs + 4 * c4);
             const float gg[4] = {gv.x, gv.y, gv.z, gv.w}, xx[4] = {xv.x, xv.y, xv.z, xv.w};
+            float yy[4] = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (YM) { const float4 yv = *reinterpret_cast<const float4 *>(y + ((size_t)b * HW + p) * y_cs + 4 * c4); yy[0] = yv.x; yy[1] = yv.y; yy[2] = yv.z; yy[3] = yv.w; }
 #pragma unroll
             for (int k = 0; k < 4; k++)
-                if (gnb_mask(xx[k], st[k], gm[k], bt[k])) {
+                if (YM ? yy[k] > 0.f : gnb_mask(xx[k], st[k], gm[k], bt[k])) {
                     sa[k] += (double)gg[k];
                     sb[k] += (double)gg[k] * (((double)xx[k] - (double)st[k].x) * (double)st[k].y);
                 }
@@ -292,9 +296,10 @@ __global__ __launch_bounds__(64) void gnb_param_kernel(const double *__restrict_
     if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)sa : (float)sa;
     if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)sb : (float)sb;
 }
+template <bool YM>
 __global__ __launch_bounds__(256) void gnb_apply_kernel(const float *__restrict__ g, int g_cs, const float *__restrict__ x, int x_cs, const float2 *__restrict__ stats,
                                                         const float *__restrict__ gamma, const float *__restrict__ beta, const double *__restrict__ gsum, int groups,
-                                                        int B, int HW, int C, const float *base, int base_cs, float *dx, int dx_cs)
+                                                        int B, int HW, int C, const float *base, int base_cs, float *dx, int dx_cs, const float *__restrict__ y, int y_cs)
 {
     const int C4 = C >> 2, cg = C / groups;
     const long t = (long)blockIdx.x * 256 + threadIdx.x, total = (long)B * HW * C4;
@@ -305,6 +310,8 @@ __global__ __launch_bounds__(256) void gnb_apply_kernel(const float *__restrict_
     float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (base) bv = *reinterpret_cast<const float4 *>(base + pix * base_cs + 4 * c4);       // may alias dx: each element is read and written by this thread only
     const float gg[4] = {gv.x, gv.y, gv.z, gv.w}, xx[4] = {xv.x, xv.y, xv.z, xv.w}, bb[4] = {bv.x, bv.y, bv.z, bv.w};
+    float yy[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (YM) { const float4 yv = *reinterpret_cast<const float4 *>(y + pix * y_cs + 4 * c4); yy[0] = yv.x; yy[1] = yv.y; yy[2] = yv.z; yy[3] = yv.w; }
     const double inv_n = 1.0 / ((double)HW * cg);
     float o[4];
 #pragma unroll
@@ -313,7 +320,7 @@ __global__ __launch_bounds__(256) void gnb_apply_kernel(const float *__restrict_
         const float2 st = stats[gi];
         const float gm = gamma[c];
         const double xhat = ((double)xx[k] - (double)st.x) * (double)st.y;
-        const double e = gnb_mask(xx[k], st, gm, beta[c]) ? (double)gg[k] * (double)gm : 0.0;
+        const double e = (YM ? yy[k] > 0.f : gnb_mask(xx[k], st, gm, beta[c])) ? (double)gg[k] * (double)gm : 0.0;
         const float d = (float)((double)st.y * (e - (gsum[2 * gi] + xhat * gsum[2 * gi + 1]) * inv_n));
         o[k] = base ? bb[k] + d : d;
     }
@@ -369,17 +376,21 @@ static int wgrad(bool k3, const float *d_out, int do_cs, int do_co, const float 
     return VT_OK;
 }
 static int gnb(const float *g, int g_cs, const float *x, int x_cs, const float *gn_stats, const float *gamma, const float *beta, int groups, int B, int HW, int C,
-               const float *base, int base_cs, float *dx, int dx_cs, float *dgamma, float *dbeta, int accumulate, void *ws, hipStream_t st)
+               const float *base, int base_cs, float *dx, int dx_cs, float *dgamma, float *dbeta, int accumulate, void *ws, hipStream_t st,
+               const float *y = nullptr, int y_cs = 0)
 {
     const int nblk = gnb_blocks(HW), rows = (HW + nblk - 1) / nblk;
     double *part = static_cast<double *>(ws), *gsum = part + (size_t)nblk * B * C * 2;
     const float2 *st2 = reinterpret_cast<const float2 *>(gn_stats);
-    hipLaunchKernelGGL(gnb_reduce_kernel, dim3(nblk, B), dim3(256), 0, st, g, g_cs, x, x_cs, st2, gamma, beta, groups, HW, C, rows, part);
+    if (y) hipLaunchKernelGGL(gnb_reduce_kernel<true>, dim3(nblk, B), dim3(256), 0, st, g, g_cs, x, x_cs, st2, gamma, beta, groups, HW, C, rows, part, y, y_cs);
+    else hipLaunchKernelGGL(gnb_reduce_kernel<false>, dim3(nblk, B), dim3(256), 0, st, g, g_cs, x, x_cs, st2, gamma, beta, groups, HW, C, rows, part, y, y_cs);
     if (dgamma || dbeta) hipLaunchKernelGGL(gnb_param_kernel, dim3((C + 63) / 64), dim3(64), 0, st, part, nblk, B, C, dgamma, dbeta, accumulate);
     if (dx) {
         hipLaunchKernelGGL(gnb_group_kernel, dim3(B * groups), dim3(64), 0, st, part, nblk, B, C, groups, gamma, gsum);
         const long total = (long)B * HW * (C >> 2);
-        hipLaunchKernelGGL(gnb_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, g, g_cs, x, x_cs, st2, gamma, beta, gsum, groups, B, HW, C, base, base_cs, dx, dx_cs);
+        const dim3 ag((unsigned)((total + 255) / 256));
+        if (y) hipLaunchKernelGGL(gnb_apply_kernel<true>, ag, dim3(256), 0, st, g, g_cs, x, x_cs, st2, gamma, beta, gsum, groups, B, HW, C, base, base_cs, dx, dx_cs, y, y_cs);
+        else hipLaunchKernelGGL(gnb_apply_kernel<false>, ag, dim3(256), 0, st, g, g_cs, x, x_cs, st2, gamma, beta, gsum, groups, B, HW, C, base, base_cs, dx, dx_cs, y, y_cs);
     }
     VT_LAUNCH_CHECK();
     return VT_OK;
@@ -451,6 +462,22 @@ int vt_gn_relu_backward(const float *g, int g_cstride, int g_coff, const float *
     VT_REQUIRE(!base || (d_x && convt::slice_ok(base, base_cstride, base_coff, C)), "vt_gn_relu_backward: bad base slice");
     return convt::gnb(g + g_coff, g_cstride, x_in + x_coff, x_cstride, gn_stats, gamma, beta, groups, B, HW, C, base ? base + base_coff : nullptr, base_cstride,
                       d_x ? d_x + dx_coff : nullptr, dx_cstride, dgamma, dbeta, accumulate, workspace, vt_stream(stream));
+}
+// the same passes with m = [y > 0] read from the forward's saved output (the stem's bn1 + ReLU runs on vt_groupnorm_nhwc, whose expression is not the staging one)
+int vt_gn_relu_backward_y(const float *g, int g_cstride, int g_coff, const float *x_in, int x_cstride, int x_coff, const float *y, int y_cstride, int y_coff,
+                          const float *gn_stats, const float *gamma, int groups, int B, int HW, int C, const float *base, int base_cstride, int base_coff,
+                          float *d_x, int dx_cstride, int dx_coff, float *dgamma, float *dbeta, int accumulate, void *workspace, void *stream)
+{
+    VT_REQUIRE(gn_stats && gamma && workspace && B > 0 && B <= 65535 && HW > 0 && C >= 4 && C <= 1024 && C % 4 == 0 && groups > 0 && C % groups == 0,
+               "vt_gn_relu_backward_y: needs statistics, gamma, a workspace, C %% 4 == 0, C <= 1024 and C %% groups == 0");
+    VT_REQUIRE(convt::slice_ok(g, g_cstride, g_coff, C) && convt::slice_ok(x_in, x_cstride, x_coff, C) && convt::slice_ok(y, y_cstride, y_coff, C),
+               "vt_gn_relu_backward_y: needs 16-byte aligned channel slices");
+    VT_REQUIRE(d_x || dgamma || dbeta, "vt_gn_relu_backward_y: nothing to compute");
+    VT_REQUIRE(!d_x || convt::slice_ok(d_x, dx_cstride, dx_coff, C), "vt_gn_relu_backward_y: bad d_x slice");
+    VT_REQUIRE(!base || (d_x && convt::slice_ok(base, base_cstride, base_coff, C)), "vt_gn_relu_backward_y: bad base slice");
+    // beta only enters the mask, which comes from y here: gamma stands in for the pointer the shared passes never read in this form
+    return convt::gnb(g + g_coff, g_cstride, x_in + x_coff, x_cstride, gn_stats, gamma, gamma, groups, B, HW, C, base ? base + base_coff : nullptr, base_cstride,
+                      d_x ? d_x + dx_coff : nullptr, dx_cstride, dgamma, dbeta, accumulate, workspace, vt_stream(stream), y + y_coff, y_cstride);
 }
 
 // workspace of the block: G (the gradient to a rectified activation, the widest of Cin and c1 channels), D (d_o1 | d_o2 = the dy slices + what the later

@@ -504,6 +504,181 @@ class TrainableHourglass:
         return self._level(self.depth, x)
 
 
+def _leaf(v, device):
+    return torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).detach().to(device=device, dtype=torch.float32).contiguous().clone().requires_grad_(True)
+
+
+class _PackedHandles:
+    """packed forward handles of (weight, bias) leaf pairs, rebuilt on the HOST from a pair whose version counters changed since it was packed (known and not
+    done: the device-side repack, see ``TrainableConvBlock``)"""
+
+    def _init_handles(self):
+        self._handles = {}          # key -> [handle, (weight version, bias version), destroy]
+
+    def _packed(self, key, w, b, create, destroy, device):
+        import ctypes as C
+        ent = self._handles.get(key)
+        ver = (w._version, b._version)
+        if ent is None or ent[1] != ver:
+            if ent is not None:
+                torch.cuda.synchronize(device)          # launches that read the old packing may still be queued
+                destroy(ent[0])
+            cout, cin = w.shape[:2]
+            wh = np.ascontiguousarray(w.detach().cpu().numpy().reshape(cout, cin, -1), np.float32)
+            bh = np.ascontiguousarray(b.detach().cpu().numpy(), np.float32)
+            h = C.c_void_p()
+            with torch.cuda.device(device):
+                L.check(create(C.byref(h), wh.ctypes.data, bh.ctypes.data, cout, cin, L.stream_ptr()))
+            ent = self._handles[key] = [h, ver, destroy]
+        return ent[0]
+
+    def __del__(self):
+        try:
+            for h, _, destroy in getattr(self, "_handles", {}).values():
+                destroy(h)
+        except Exception:
+            pass
+
+
+class TrainableStem(_PackedHandles):
+    """conv1 + bn1 + ReLU (model/HGFilters.py:120-125, 167) with the four parameters as fp32 device leaves under the keys of ``ops.STEM_PARAMS``; differentiable
+    through ``ops.stem_train``."""
+
+    def __init__(self, leaves: dict, device):
+        self.device = torch.device(device)
+        self.leaves = leaves
+        self._init_handles()
+
+    def tensors(self):
+        return [self.leaves[k] for k in ops.STEM_PARAMS]
+
+    def parameters(self):
+        return self.tensors()
+
+    def handle(self, device):
+        lib = L.lib()
+        return self._packed("conv1", self.leaves["conv1.weight"], self.leaves["conv1.bias"], lib.vt_stem7x7_create, lib.vt_stem7x7_destroy, device)
+
+    def __call__(self, x):
+        return ops.stem_train(x, self)
+
+
+class TrainableStackTail(_PackedHandles):
+    """conv_last, bn_end, l and, before the last stack, bl and al of one stack (model/HGFilters.py:146-160, 191-201) as fp32 device leaves under the keys of
+    ``ops.STACK_TAIL_PARAMS`` (the reference's names without the stack index); differentiable through ``ops.stack_tail_train``."""
+
+    def __init__(self, leaves: dict, last: bool, device):
+        self.device = torch.device(device)
+        self.leaves = leaves
+        self.last = bool(last)
+        self._init_handles()
+
+    def tensors(self):
+        return [self.leaves.get(k) for k in ops.STACK_TAIL_PARAMS]
+
+    def parameters(self):
+        return [t for t in self.tensors() if t is not None]
+
+    def handles(self, device):
+        lib = L.lib()
+        return [self._packed(n, self.leaves[n + ".weight"], self.leaves[n + ".bias"], lib.vt_conv1x1_create, lib.vt_conv1x1_destroy, device) if n + ".weight" in self.leaves else None
+                for n in ("conv_last", "l", "bl", "al")]
+
+    def __call__(self, ll, previous=None):
+        return ops.stack_tail_train(ll, previous, self, self.last)
+
+
+class TrainableHGFilter:
+    """The reference's ``HGFilter`` (model/HGFilters.py:56-203; norm='group', hg_down='ave_pool') that trains: every parameter an fp32 device leaf, the forward
+    the launches of ``HGFilterEncoder.__call__`` bit for bit, the backward entirely on the library's kernels.  Built from a ``TrainableStem`` (``.stem``),
+    ``TrainableConvBlock``s (``.blocks``: 'conv2', 'conv3', 'conv4', 'top_m_i'), ``TrainableHourglass``es (``.hourglasses[i]`` = m_i) and ``TrainableStackTail``s
+    (``.tails[i]``), joined by ``ops.avgpool2x2_train``.
+
+        enc = TrainableHGFilter.from_state_dict(sd, "image_filter.", num_stack=3, num_hourglass=2)
+        outputs, tmpx, normx = enc(images)          # tmpx is detached (HGFilters.py:203); outputs and normx carry autograd
+        loss.backward()                             # p.grad for p in enc.parameters()
+
+    Serves the image encoder (Cin 5, tmpx 64) and the triplane encoder (Cin 1, tmpx 32).  The input needs H % 32 == 0 and W % 64 == 0 times 2^num_hourglass for
+    the innermost level of an hourglass to be a multiple of 8 x 16.
+
+    KNOWN AND NOT DONE: the packed forward handles are rebuilt on the HOST after an optimiser step (see ``TrainableConvBlock``); the device-side repack is the one
+    row of the encoder that remains."""
+
+    def __init__(self, stem, blocks, hourglasses, tails, num_hourglass, device):
+        self.device = torch.device(device)
+        self.stem, self.blocks, self.hourglasses, self.tails = stem, blocks, hourglasses, tails
+        self.num_stack, self.depth = len(tails), int(num_hourglass)
+
+    @classmethod
+    def from_state_dict(cls, sd, prefix="", num_stack=3, num_hourglass=2, device="cuda:0"):
+        """``sd``: tensors or arrays under the reference's keys; ``prefix`` e.g. 'image_filter.' or 'triplane_encoder.' (a leading 'module.' is stripped)"""
+        own = {}
+        for k, v in sd.items():
+            k = k[7:] if k.startswith("module.") else k
+            if k.startswith(prefix):
+                own[k[len(prefix):]] = v
+
+        def need(k):
+            if k not in own:
+                raise KeyError(f"no encoder parameter '{prefix}{k}'")
+            return _leaf(own[k], device)
+
+        stem = TrainableStem({k: need(k) for k in ops.STEM_PARAMS}, device)
+        blocks = {n: TrainableConvBlock.from_state_dict(own, n + ".", device=device) for n in ["conv2", "conv3", "conv4"] + [f"top_m_{i}" for i in range(num_stack)]}
+        hgs = [TrainableHourglass.from_state_dict(own, f"m{i}.", depth=num_hourglass, device=device) for i in range(num_stack)]
+        tails = []
+        for i in range(num_stack):
+            last = i == num_stack - 1
+            names = ("conv_last", "bn_end", "l") + (() if last else ("bl", "al"))
+            tails.append(TrainableStackTail({f"{n}.{s}": need(f"{n}{i}.{s}") for n in names for s in ("weight", "bias")}, last, device))
+        return cls(stem, blocks, hgs, tails, num_hourglass, device)
+
+    def state_dict(self):
+        """the reference's keys (HGFilter.state_dict())"""
+        out = {k: v.detach().clone() for k, v in self.stem.leaves.items()}
+        for n, blk in self.blocks.items():
+            out.update({f"{n}.{k}": v for k, v in blk.state_dict().items()})
+        for i, (hg, tail) in enumerate(zip(self.hourglasses, self.tails)):
+            out.update({f"m{i}.{k}": v for k, v in hg.state_dict().items()})
+            for k, v in tail.leaves.items():
+                n, s = k.split(".")
+                out[f"{n}{i}.{s}"] = v.detach().clone()
+        return out
+
+    def named_parameters(self):
+        """(reference key, leaf) of every parameter an optimiser updates"""
+        out = list(self.stem.leaves.items())
+        for n, blk in self.blocks.items():
+            out += [(f"{n}.{k}", v) for k, v in blk.leaves.items() if blk.has_proj or not k.startswith("bn4.")]
+        for i, (hg, tail) in enumerate(zip(self.hourglasses, self.tails)):
+            for bn, blk in hg.blocks.items():
+                out += [(f"m{i}.{bn}.{k}", v) for k, v in blk.leaves.items() if blk.has_proj or not k.startswith("bn4.")]
+            for k, v in tail.leaves.items():
+                n, s = k.split(".")
+                out.append((f"{n}{i}.{s}", v))
+        return out
+
+    def parameters(self):
+        return [v for _, v in self.named_parameters()]
+
+    def __call__(self, x):
+        """x (B,Cin,H,W) -> (outputs [num_stack x (B,hourglass_dim,H/4,W/4)], tmpx (B,tmpx_dim,H/2,W/2) detached, normx (B,128,H/4,W/4)); channels-last"""
+        x = x.to(self.device).float().contiguous(memory_format=torch.channels_last)
+        t = self.stem(x)
+        tmpx = t.detach()
+        normx = ops.avgpool2x2_train(self.blocks["conv2"](t))
+        previous = self.blocks["conv4"](self.blocks["conv3"](normx))
+        outputs = []
+        for i, (hg, tail) in enumerate(zip(self.hourglasses, self.tails)):
+            ll = self.blocks[f"top_m_{i}"](hg(previous))
+            if tail.last:
+                outputs.append(tail(ll))
+            else:
+                out, previous = tail(ll, previous)
+                outputs.append(out)
+        return outputs, tmpx, normx
+
+
 class SIFNetEncoder:
     """``CHORETriplane.filter`` (chore_triplane.py:60-95): image encoder on channels 0..4, the (shared or per-view) triplane encoder on
     channels 5, 6, 7; returns the eight feature maps of the query as an ``ops.FeatureMaps`` (NHWC, resident on the device)."""

@@ -1073,6 +1073,217 @@ def upsample2x_bicubic_add_train(low, skip):
 
 
 # --------------------------------------------------------------------------------------------------
+# the stem and the 1 x 1 tail of a stack (model/HGFilters.py:120-125, 167 and 191-201), trainable
+# --------------------------------------------------------------------------------------------------
+STEM_PARAMS = ("conv1.weight", "conv1.bias", "bn1.weight", "bn1.bias")
+STACK_TAIL_PARAMS = ("conv_last.weight", "conv_last.bias", "bn_end.weight", "bn_end.bias", "l.weight", "l.bias", "bl.weight", "bl.bias", "al.weight", "al.bias")
+# outputs of vt_stack_tail_backward in argument order, and the parameter each one is the gradient of
+STACK_TAIL_GRADS = ("d_ll", "dWcl", "dbcl", "dgamma", "dbeta", "dWl", "dbl", "dWbl", "dbbl", "dWal", "dbal")
+_TAIL_GRAD_OF = dict(zip(("conv_last.weight", "conv_last.bias", "bn_end.weight", "bn_end.bias", "l.weight", "l.bias", "bl.weight", "bl.bias", "al.weight", "al.bias"),
+                         STACK_TAIL_GRADS[1:]))
+
+
+def _ws(nbytes, device, what):
+    if nbytes < 0:
+        raise L.VtError(f"{what}: unsupported shape")
+    return torch.empty(int(nbytes) // 4 + 4, device=device)
+
+
+def bias_grad(d_out, C=None, coff=0, out=None, accumulate=0):
+    """one vt_bias_grad call: db[c] = sum over (b, pixel) of channels [coff, coff + C) of the channels-last (B,Ct,H,W) tensor d_out"""
+    d = _resample_arg("bias_grad", d_out)
+    B, Ct, H, W = d.shape
+    C = Ct - coff if C is None else int(C)
+    db = torch.empty(C, device=d.device) if out is None else out
+    with torch.cuda.device(d.device):
+        ws = _ws(L.lib().vt_bias_grad_workspace_bytes(B, H * W, C), d.device, f"bias_grad: {C} channels at {H}x{W}")
+        L.check(L.lib().vt_bias_grad(d.data_ptr(), Ct, int(coff), B, H * W, C, db.data_ptr(), int(accumulate), ws.data_ptr(), L.stream_ptr()))
+    return db
+
+
+def stem7x7_wgrad(d_y, x, out=None, accumulate=0):
+    """one vt_stem7x7_wgrad call: d_y (B,Cout,H2,W2) and x (B,Cin,H,W) channels-last -> dW (Cout,Cin,7,7) of conv1 = Conv2d(Cin, Cout, 7, stride 2, padding 3)"""
+    d, xc = _resample_arg("stem7x7_wgrad", d_y), _resample_arg("stem7x7_wgrad", x)
+    B, cin, H, W = xc.shape
+    cout = d.shape[1]
+    if tuple(d.shape) != (B, cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1):
+        raise L.VtError(f"stem7x7_wgrad: d_y {tuple(d.shape)} does not belong to an input {tuple(xc.shape)}")
+    dW = torch.empty(cout, cin, 7, 7, device=d.device) if out is None else out
+    with torch.cuda.device(d.device):
+        ws = _ws(L.lib().vt_stem7x7_wgrad_workspace_bytes(B, H, W, cin, cout), d.device, f"stem7x7_wgrad: {cin}->{cout} at {H}x{W}")
+        L.check(L.lib().vt_stem7x7_wgrad(d.data_ptr(), cout, 0, xc.data_ptr(), cin, 0, B, H, W, cin, cout, dW.data_ptr(), int(accumulate), ws.data_ptr(), L.stream_ptr()))
+    return dW
+
+
+def gn_relu_backward_y(g, x_in, y, stats, gamma, groups=32, want_dx=True, accumulate=0, dgamma=None, dbeta=None):
+    """one vt_gn_relu_backward_y call: the backward of y = ReLU(GroupNorm(x_in)) with the mask read from the saved y.  g, x_in, y channels-last (B,C,H,W);
+    stats the {mean, rstd} area the forward left.  -> (d_x or None, dgamma, dbeta)"""
+    gc, xc, yc = (_resample_arg("gn_relu_backward_y", t) for t in (g, x_in, y))
+    B, C, H, W = xc.shape
+    d_x = torch.empty_like(xc, memory_format=torch.channels_last) if want_dx else None
+    dgamma = torch.empty(C, device=xc.device) if dgamma is None else dgamma
+    dbeta = torch.empty(C, device=xc.device) if dbeta is None else dbeta
+    with torch.cuda.device(xc.device):
+        ws = _ws(L.lib().vt_gn_relu_backward_workspace_bytes(B, H * W, C, groups), xc.device, f"gn_relu_backward_y: {C} channels in {groups} groups")
+        L.check(L.lib().vt_gn_relu_backward_y(gc.data_ptr(), C, 0, xc.data_ptr(), C, 0, yc.data_ptr(), C, 0, stats.data_ptr(), gamma.data_ptr(), groups, B, H * W, C,
+                                              None, 0, 0, d_x.data_ptr() if want_dx else None, C, 0, dgamma.data_ptr(), dbeta.data_ptr(), int(accumulate),
+                                              ws.data_ptr(), L.stream_ptr()))
+    return d_x, dgamma, dbeta
+
+
+def stack_tail_backward_raw(d_out, d_prev, ll, raw, out, stats, params, want=None, res=None, accumulate=0):
+    """one vt_stack_tail_backward call.  d_out (B,Co,H,W) / d_prev (B,C,H,W) or None; ll, raw, out the forward's tensors (channels-last); stats the {mean, rstd}
+    area of bn_end; params: dict over STACK_TAIL_PARAMS (the bl / al entries None on the last stack); ``want``: names out of STACK_TAIL_GRADS (default: all that
+    exist); ``res``: preallocated outputs by name (accumulate != 0 adds onto the parameter gradients in them).  -> dict name -> tensor"""
+    lib = L.lib()
+    B, C, H, W = ll.shape
+    Co = int(params["l.weight"].shape[0])
+    mid = d_prev is not None
+    names = [n for n in STACK_TAIL_GRADS if mid or n not in ("dWbl", "dbbl", "dWal", "dbal")]
+    want = names if want is None else [n for n in names if n in want]
+    like = {"d_ll": ll}
+    like.update({g: params.get(k) for k, g in _TAIL_GRAD_OF.items()})
+    got = dict(res or {})
+    for n in want:
+        if n not in got:
+            got[n] = torch.empty_like(like[n], memory_format=torch.channels_last if n == "d_ll" else torch.contiguous_format)
+    ptr = lambda t: None if t is None else t.data_ptr()         # noqa: E731
+    with torch.cuda.device(ll.device):
+        ws = _ws(lib.vt_stack_tail_backward_workspace(B, H, W, C, Co), ll.device, f"stack_tail_backward: {C} / {Co} channels at {H}x{W}")
+        L.check(lib.vt_stack_tail_backward(ptr(d_out), ptr(d_prev), ll.data_ptr(), raw.data_ptr(), ptr(out), stats.data_ptr(),
+                                           *[ptr(params.get(k)) for k in ("conv_last.weight", "bn_end.weight", "bn_end.bias", "l.weight", "bl.weight", "al.weight")],
+                                           B, H, W, C, Co, *[ptr(got.get(n)) if n in want else None for n in STACK_TAIL_GRADS], ws.data_ptr(), int(accumulate), L.stream_ptr()))
+    return {n: got[n] for n in want}
+
+
+class _StemTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mod, x, w, b, gamma, beta):
+        # the launches of HGFilterEncoder._stem + _gn(..., relu=True) (encoder.py), keeping what the backward reads: x, conv1's output, tmpx, the {mean, rstd} area
+        lib = L.lib()
+        B, cin, H, W = x.shape
+        cout = int(w.shape[0])
+        with torch.cuda.device(x.device):
+            y1 = torch.empty(B, cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1, device=x.device, memory_format=torch.channels_last)
+            L.check(lib.vt_stem7x7_forward(mod.handle(x.device), x.data_ptr(), cin, 0, B, H, W, y1.data_ptr(), cout, 0, L.stream_ptr()))
+            HW = y1.shape[2] * y1.shape[3]
+            y = torch.empty_like(y1, memory_format=torch.channels_last)
+            ws = torch.empty(lib.vt_groupnorm_workspace_doubles(B, HW, cout, 32), dtype=torch.float64, device=x.device)
+            L.check(lib.vt_groupnorm_nhwc(y1.data_ptr(), gamma.data_ptr(), beta.data_ptr(), B, HW, cout, 32, 1e-5, 1, ws.data_ptr(), y.data_ptr(), L.stream_ptr()))
+        ctx.save_for_backward(x, y1, y, ws, gamma)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y1, y, ws, gamma = ctx.saved_tensors
+        need = ctx.needs_input_grad[2:]
+        if not any(need):
+            return (None,) * 6
+        dy = dy.float().contiguous(memory_format=torch.channels_last)
+        d_y1, dgamma, dbeta = gn_relu_backward_y(dy, y1, y, ws, gamma, 32, want_dx=need[0] or need[1])
+        dW = stem7x7_wgrad(d_y1, x) if need[0] else None
+        db = bias_grad(d_y1) if need[1] else None
+        return None, None, dW, db, (dgamma if need[2] else None), (dbeta if need[3] else None)
+
+
+def stem_train(x, module):
+    """``F.relu(bn1(conv1(x)))`` (model/HGFilters.py:167) that a torch graph can contain.  ``x``: (B,Cin,H,W) device tensor; ``module``: an
+    ``encoder.TrainableStem`` (its leaves ``tensors()`` in STEM_PARAMS order and the packed forward handle ``handle(device)``).  Forward: exactly the launches of
+    ``HGFilterEncoder._stem`` + ``_gn(..., relu=True)``; backward: vt_gn_relu_backward_y (mask from the saved output), vt_bias_grad and vt_stem7x7_wgrad.  The image
+    receives no gradient."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
+        raise L.VtError("stem_train: x must be a (B,C,H,W) device tensor; there is no CPU path")
+    w, b, gamma, beta = module.tensors()
+    cout, cin = int(w.shape[0]), int(w.shape[1])
+    if cout not in (32, 64) or not 1 <= cin <= 8 or tuple(w.shape[2:]) != (7, 7) or x.shape[1] != cin:
+        raise L.VtError(f"stem_train: a {tuple(w.shape)} stem on an input with {x.shape[1]} channels is not served (Cout in {{32, 64}}, Cin in 1..8, 7 x 7)")
+    xc = x.detach().float().contiguous(memory_format=torch.channels_last)
+    return _StemTrainFn.apply(module, xc, w, b, gamma, beta)
+
+
+class _StackTailTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mod, last, ll, previous, *tensors):
+        # the four launches of the 1 x 1 tail in HGFilterEncoder.__call__ (encoder.py), keeping what the backward reads: ll, raw, out and bn_end's {mean, rstd} area
+        lib = L.lib()
+        p = dict(zip(STACK_TAIL_PARAMS, tensors))
+        B, C, H, W = ll.shape
+        Co = int(p["l.weight"].shape[0])
+        dev = ll.device
+
+        def conv(h, x, cin, cout, gn, res, want_stats):
+            o = torch.empty(B, cout, H, W, device=dev, memory_format=torch.channels_last)
+            wo = torch.empty(B * 32 + tiles * B * cout * 2, dtype=torch.float64, device=dev) if want_stats else None
+            L.check(lib.vt_conv1x1_forward(h, x.data_ptr(), cin, 0, gn.data_ptr() if gn is not None else None,
+                                           p["bn_end.weight"].data_ptr() if gn is not None else None, p["bn_end.bias"].data_ptr() if gn is not None else None, 32,
+                                           B, H, W, o.data_ptr(), cout, 0, res.data_ptr() if res is not None else None, cout, 0,
+                                           wo.data_ptr() if want_stats else None, 32, L.stream_ptr()))
+            if want_stats:
+                L.check(lib.vt_groupnorm_finalize(wo.data_ptr(), tiles, B, H * W, cout, 32, 1e-5, L.stream_ptr()))
+            return o, wo
+
+        with torch.cuda.device(dev):
+            tiles = lib.vt_conv3x3_tiles(H, W)
+            h_cl, h_l, h_bl, h_al = mod.handles(dev)
+            raw, ws = conv(h_cl, ll, C, C, None, None, True)
+            out, _ = conv(h_l, raw, C, Co, ws, None, False)
+            ctx.set_materialize_grads(False)
+            ctx.present = [t is not None for t in tensors]
+            ctx.last = bool(last)
+            if last:
+                ctx.save_for_backward(ll, raw, out, ws, *[t for t in tensors if t is not None])
+                return out
+            tmp, _ = conv(h_bl, raw, C, C, ws, previous, False)
+            prev2, ws2 = conv(h_al, out, Co, C, None, tmp, True)
+        ctx.save_for_backward(ll, raw, out, ws, *[t for t in tensors if t is not None])
+        ctx.mark_non_differentiable(ws2)
+        return out, prev2, ws2
+
+    @staticmethod
+    def backward(ctx, *gs):
+        sv = ctx.saved_tensors
+        ll, raw, out, ws = sv[:4]
+        it = iter(sv[4:])
+        p = {k: (next(it) if have else None) for k, have in zip(STACK_TAIL_PARAMS, ctx.present)}
+        d_out = gs[0]
+        d_prev = None if ctx.last else gs[1]
+        nothing = (None,) * (4 + len(STACK_TAIL_PARAMS))
+        if d_out is None and d_prev is None:
+            return nothing
+        cl = lambda t: None if t is None else t.float().contiguous(memory_format=torch.channels_last)       # noqa: E731
+        d_out, d_prev = cl(d_out), cl(d_prev)
+        need = ctx.needs_input_grad
+        want = (["d_ll"] if need[2] else []) + [_TAIL_GRAD_OF[k] for k, n in zip(STACK_TAIL_PARAMS, need[4:]) if n and p[k] is not None]
+        g = stack_tail_backward_raw(d_out, d_prev, ll, raw, out, ws, p, want=want)
+        # previous' = previous + ...: the gradient to `previous` is d_prev itself
+        return (None, None, g.get("d_ll"), d_prev if (not ctx.last and need[3]) else None, *[g.get(_TAIL_GRAD_OF[k]) for k in STACK_TAIL_PARAMS])
+
+
+def stack_tail_train(ll, previous, module, last):
+    """The tail of one stack (model/HGFilters.py:191-201) that a torch graph can contain: ``ll`` (B,C,H,W) the output of top_m, ``previous`` the stack's input
+    (ignored when ``last``), ``module`` an ``encoder.TrainableStackTail``.  -> ``out`` when ``last``, else ``(out, previous')`` with the GroupNorm statistics of
+    previous' attached for the next stack's first block.  Forward: exactly the four (two) launches of the tail in ``HGFilterEncoder.__call__``; backward: one
+    ``vt_stack_tail_backward`` call, an absent upstream gradient passed as NULL."""
+    if not (torch.is_tensor(ll) and ll.is_cuda and ll.dim() == 4):
+        raise L.VtError("stack_tail_train: ll must be a (B,C,H,W) device tensor; there is no CPU path")
+    tensors = module.tensors()
+    B, C, H, W = ll.shape
+    Co = int(tensors[4].shape[0])
+    if int(L.lib().vt_stack_tail_backward_workspace(B, H, W, C, Co)) < 0 or tuple(tensors[0].shape[:2]) != (C, C) or (tensors[6] is None) != bool(last):
+        raise L.VtError(f"stack_tail_train: a tail of {C} / {Co} channels at {H}x{W} (last={bool(last)}) is not served (H % 8 == 0, W % 16 == 0, channels in {{64, 128, 256}}, "
+                        f"bl / al exactly on the stacks before the last)")
+    llc = _resample_arg("stack_tail_train", ll)
+    if last:
+        return _StackTailTrainFn.apply(module, True, llc, None, *tensors)
+    pc = _resample_arg("stack_tail_train", previous)
+    if tuple(pc.shape) != (B, C, H, W):
+        raise L.VtError(f"stack_tail_train: previous {tuple(pc.shape)} does not fit ll {tuple(llc.shape)}")
+    out, prev2, ws2 = _StackTailTrainFn.apply(module, False, llc, pc, *tensors)
+    prev2._vt_stats = [ws2, int(L.lib().vt_conv3x3_tiles(H, W)), True]
+    return out, prev2
+
+
+# --------------------------------------------------------------------------------------------------
 # silhouette
 # --------------------------------------------------------------------------------------------------
 class _SilFn(torch.autograd.Function):
