@@ -851,6 +851,54 @@ int vt_stack_tail_backward(const float *d_out, const float *d_prev, const float 
                            float *d_ll, float *dWcl, float *dbcl, float *dgamma, float *dbeta, float *dWl, float *dbl, float *dWbl, float *dbbl, float *dWal, float *dbal,
                            void *workspace, int accumulate, void *stream);
 
+/* ---- packed forward weights built on the device (csrc/repack.hip) ------------------------------------------------------------------------------------------
+ * Replaces, for a network that trains, the host side of vt_conv3x3_create / vt_conv1x1_create / vt_stem7x7_create (no counterpart in the reference, whose
+ * nn.Conv2d reads its fp32 weight directly: model/net_util.py:213-216, HGFilters.py:120, 146-160): after an optimiser step the new weights exist only in device
+ * memory, and so does max |w|, which fixes the power-of-two scale s_W of the split-f16 kinds.  Everything below reads fp32 (Cout, Cin, k, k) weights and (Cout)
+ * biases IN DEVICE MEMORY and writes the packed bytes of the host functions bit for bit (hi = (f16)(w s_W), lo = (f16)(w s_W - hi), round to nearest even, f16
+ * denormals kept, rows beyond Cout = 32 zero; the stem: the [Cin][7][7][Cout] transpose + the bias row, zeros without a bias).  The scale rule is the host's: NaN
+ * entries do not take part in the maximum, a zero or non-finite maximum gives s_W = 1.  The split-f16 kinds also write the SCALE WORD 1 / (16 s_W) to device memory;
+ * the forward kernel reads it from there when the handle has one (handles of the host functions pass it by value as before).  A packing is two launches queued on
+ * `stream` (the maxima per workgroup without atomics, then the fragments): ordering on the stream protects launches that still read the old packing.
+ *
+ * sizes: vt_conv3x3_packed_bytes / vt_stem7x7_packed_bytes(cout, cin) = the packed bytes of a handle; vt_conv1x1_packed_bytes = of ONE of the vt_conv1x1_parts(cout)
+ *   parts (2 for Cout = 256), which lie one after the other; vt_repack_workspace_bytes() = the partial maxima.  -1 for a shape the forward does not serve.
+ * vt_*_pack: into caller-supplied device buffers (packed_dev 16-byte aligned; scale_dev one float; ws_dev vt_repack_workspace_bytes(); the 1 x 1 copies bias_dev to
+ *   bias_out_dev when both are given).
+ * vt_*_create_device: a handle for the existing forward entry points, packed from device weights: one hipMalloc, no host staging, no synchronisation.
+ * vt_*_repack: overwrite such a handle's own buffers in place; the handle's address and buffers stay.  3 x 3 and 1 x 1 need a handle of *_create_device (the host
+ *   handles have no scale word) and a bias exactly when the handle was created with one; the stem takes any handle.
+ * vt_repack_plan_*: n handles (kinds[i] one of VT_REPACK_*, handles[i], weights[i], biases[i] or NULL) repacked by vt_repack_plan_run in two launches
+ *   whatever n.  The pointers are captured at creation: the weights must stay where they are.
+ * DIAGNOSTIC ONLY, not part of the training path (used by the tests and by tools/bench_scripts/repackbench.py; may change without notice):
+ *   vt_repack_plan_launches: the number of launches of one vt_repack_plan_run; vt_repack_handle_snapshot: a handle's packed bytes (and scale word, host- or
+ *   device-made) copied to device buffers. */
+#define VT_REPACK_CONV3X3 0
+#define VT_REPACK_CONV1X1 1
+#define VT_REPACK_STEM7X7 2
+typedef struct vt_repack_plan vt_repack_plan;
+long vt_conv3x3_packed_bytes(int cout, int cin);
+long vt_conv1x1_packed_bytes(int cout, int cin);
+int vt_conv1x1_parts(int cout);
+long vt_stem7x7_packed_bytes(int cout, int cin);
+long vt_repack_workspace_bytes(void);
+int vt_conv3x3_pack(const float *w_dev, int cout, int cin, void *packed_dev, float *scale_dev, void *ws_dev, void *stream);
+int vt_conv1x1_pack(const float *w_dev, const float *bias_dev, int cout, int cin, void *packed_dev, float *bias_out_dev, float *scale_dev, void *ws_dev,
+                    void *stream);
+int vt_stem7x7_pack(const float *w_dev, const float *bias_dev, int cout, int cin, void *packed_dev, void *stream);
+int vt_conv3x3_create_device(vt_conv3x3 **out, const float *w_dev, int cout, int cin, void *stream);
+int vt_conv1x1_create_device(vt_conv1x1 **out, const float *w_dev, const float *bias_dev, int cout, int cin, void *stream);
+int vt_stem7x7_create_device(vt_stem7x7 **out, const float *w_dev, const float *bias_dev, int cout, int cin, void *stream);
+int vt_conv3x3_repack(vt_conv3x3 *h, const float *w_dev, void *stream);
+int vt_conv1x1_repack(vt_conv1x1 *h, const float *w_dev, const float *bias_dev, void *stream);
+int vt_stem7x7_repack(vt_stem7x7 *h, const float *w_dev, const float *bias_dev, void *stream);
+int vt_repack_plan_create(vt_repack_plan **out, int n, const int *kinds, void *const *handles, const float *const *weights, const float *const *biases);
+int vt_repack_plan_run(const vt_repack_plan *plan, void *stream);
+void vt_repack_plan_destroy(vt_repack_plan *plan);
+/* diagnostic only (see above) */
+int vt_repack_plan_launches(const vt_repack_plan *plan);
+int vt_repack_handle_snapshot(int kind, const void *handle, void *packed_out_dev, float *scale_out_dev, void *stream);
+
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two
  * workgroups of 256 threads per CU, non-trivial operands), out[1] = shader clock sustained during it (MHz: s_memtime against the 100 MHz s_memrealtime),

@@ -183,6 +183,26 @@ SIGNATURES = {
     "vt_stack_tail_backward_workspace": (cl, [ci, ci, ci, ci, ci]),
     # d_out, d_prev, ll, raw, out, stats | wcl, gamma, beta, wl, wbl, wal | B, H, W, C, Co | d_ll, dWcl, dbcl, dgamma, dbeta, dWl, dbl, dWbl, dbbl, dWal, dbal | ws, accumulate, stream
     "vt_stack_tail_backward": (ci, [fp] * 6 + [fp] * 6 + [ci] * 5 + [fp] * 11 + [vp, ci, vp]),
+    # csrc/repack.hip: the packed forward weights built on the device (replaces the host side of vt_conv3x3_create / vt_conv1x1_create / vt_stem7x7_create)
+    "vt_conv3x3_packed_bytes": (cl, [ci, ci]),
+    "vt_conv1x1_packed_bytes": (cl, [ci, ci]),
+    "vt_conv1x1_parts": (ci, [ci]),
+    "vt_stem7x7_packed_bytes": (cl, [ci, ci]),
+    "vt_repack_workspace_bytes": (cl, []),
+    "vt_conv3x3_pack": (ci, [fp, ci, ci, fp, fp, fp, vp]),                      # w, cout, cin | packed, scale, ws | stream
+    "vt_conv1x1_pack": (ci, [fp, fp, ci, ci, fp, fp, fp, fp, vp]),              # w, bias, cout, cin | packed, bias_out, scale, ws | stream
+    "vt_stem7x7_pack": (ci, [fp, fp, ci, ci, fp, vp]),                          # w, bias, cout, cin | packed | stream
+    "vt_conv3x3_create_device": (ci, [C.POINTER(vp), fp, ci, ci, vp]),
+    "vt_conv1x1_create_device": (ci, [C.POINTER(vp), fp, fp, ci, ci, vp]),
+    "vt_stem7x7_create_device": (ci, [C.POINTER(vp), fp, fp, ci, ci, vp]),
+    "vt_conv3x3_repack": (ci, [vp, fp, vp]),
+    "vt_conv1x1_repack": (ci, [vp, fp, fp, vp]),
+    "vt_stem7x7_repack": (ci, [vp, fp, fp, vp]),
+    "vt_repack_plan_create": (ci, [C.POINTER(vp), ci, C.POINTER(ci), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "vt_repack_plan_launches": (ci, [vp]),
+    "vt_repack_plan_run": (ci, [vp, vp]),
+    "vt_repack_plan_destroy": (None, [vp]),
+    "vt_repack_handle_snapshot": (ci, [ci, vp, fp, fp, vp]),
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
 }

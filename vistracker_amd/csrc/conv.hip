@@ -14,23 +14,16 @@
 //     -- the ConvBlock's torch.cat of its three outputs is free.
 // Activations are scaled by 2^4 (|x| < 4094; a value beyond the fp16 range poisons the tile's output with NaN -- loud), weights per layer to
 // [2^13, 2^14); both scales are powers of two and undone exactly in the epilogue.
-#include "common.h"
+#include "conv_handles.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 #define MFMAH(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-#define CV_ACT_SCALE 16.0f
 #define CV_TH 8
 #define CV_TW 16
 #define CV_PW (CV_TW + 2)
 #define CV_PX ((CV_TH + 2) * CV_PW)         /* 180 halo pixels */
 #define CV_SPLIT_MAX 65504.0f
-
-struct vt_conv3x3 {
-    uint4 *w;           // [Cin / 32][9][4 waves][NT][hi|lo][64 lanes]
-    int cin, cout, nt;
-    float inv_scale;    // 1 / (CV_ACT_SCALE * s_W)
-};
 
 __device__ __forceinline__ h8 cv_h8(const uint4 v) { return __builtin_bit_cast(h8, v); }
 __device__ __forceinline__ void cv_split2(float x0, float x1, unsigned &hi, unsigned &lo, float &rmax)
@@ -58,10 +51,10 @@ __device__ __forceinline__ float cv_row16_sum(float v)
 template <int NT, bool K3, int NCH>
 __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const float *__restrict__ in, int in_cstride, int in_coff, int H, int W, int Cin, const uint4 *__restrict__ wpk,
                                                          const float2 *__restrict__ gn_stats, const float *__restrict__ gamma, const float *__restrict__ beta, int groups,
-                                                         float *__restrict__ out, int out_cstride, int out_coff, float inv_scale, int cout, double *__restrict__ stats_part,
+                                                         float *__restrict__ out, int out_cstride, int out_coff, float inv_scale_host, int cout, double *__restrict__ stats_part,
                                                          const float *__restrict__ res, int res_cstride, int res_coff, float *__restrict__ fin, int fin_cstride, int fin_coff,
                                                          const float *__restrict__ bias, int stats_cstride, int stats_coff,
-                                                         double *__restrict__ fstats_part, int fstats_cstride, int fstats_coff)
+                                                         double *__restrict__ fstats_part, int fstats_cstride, int fstats_coff, const float *__restrict__ scale_dev)
 {
     constexpr int PW = K3 ? CV_PW : CV_TW, PX = K3 ? CV_PX : CV_TH * CV_TW, NLD = K3 ? 6 : 4, NTAP = K3 ? 9 : 1;
     // 1 x 1 form: one tap per chunk makes an iteration nine times shorter than the 3 x 3 one, so the input loads run RING - 1 = 3 chunks ahead of
@@ -209,7 +202,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const float *__restrict
     float *__restrict__ ob = out ? out + (size_t)b * H * W * out_cstride + out_coff : nullptr;
     float *__restrict__ fb = fin ? fin + (size_t)b * H * W * fin_cstride + fin_coff : nullptr;
     const float *__restrict__ rb = fin ? res + (size_t)b * H * W * res_cstride + res_coff : nullptr;
-    float bv[NT][4];                                            // bias of this lane's four output channels per channel tile (0 without one)
+    // 1 / (CV_ACT_SCALE * s_W): by value from a handle packed on the host, from the handle's device word when the weights were packed on the device (repack.hip).
+    // Read here, with the epilogue's other arguments: a test of the pointer at the top of the kernel would put a wait in front of every other kernel-argument load.
+    const float inv_scale = scale_dev ? *scale_dev : inv_scale_host;
+    float bv[NT][4];                                           // bias of this lane's four output channels per channel tile (0 without one)
 #pragma unroll
     for (int nt = 0; nt < NT; nt++)
 #pragma unroll
@@ -298,8 +294,7 @@ extern "C" int vt_conv3x3_create(vt_conv3x3 **out, const float *weight, int cout
     const int nt = cout == 128 ? 2 : 1, nchunk = cin / 32;
     float m = 0.f;
     for (size_t i = 0; i < (size_t)cout * cin * 9; i++) m = fmaxf(m, fabsf(weight[i]));
-    float sw = 1.0f;
-    if (m > 0.f && std::isfinite(m)) { int e; frexpf(m, &e); sw = ldexpf(1.0f, 14 - e); }
+    const float sw = cv_weight_scale(m);
     const size_t n16 = (size_t)nchunk * 9 * 4 * nt * 2 * 64;            // uint4 count
     _Float16 *host = new _Float16[n16 * 8];
     // fragment (step = chunk * 9 + tap, wave, nt, hi|lo, lane) halves t: W[cout = (wave nt_count + nt) 16 + (lane & 15)][cin = 32 chunk + 8 (lane >> 4) + t][tap]
@@ -315,11 +310,12 @@ extern "C" int vt_conv3x3_create(vt_conv3x3 **out, const float *weight, int cout
     VT_HIP(hipMemcpyAsync(h->w, host, n16 * 16, hipMemcpyHostToDevice, vt_stream(stream)));
     VT_HIP(hipStreamSynchronize(vt_stream(stream)));
     delete[] host;
-    h->cin = cin; h->cout = cout; h->nt = nt; h->inv_scale = 1.0f / (CV_ACT_SCALE * sw);
+    h->cin = cin; h->cout = cout; h->nt = nt; h->inv_scale = cv_inv_scale(sw);
+    h->scale = nullptr; h->part = nullptr; h->dev = nullptr;
     *out = h;
     return VT_OK;
 }
-extern "C" void vt_conv3x3_destroy(vt_conv3x3 *h) { if (!h) return; (void)hipFree(h->w); delete h; }
+extern "C" void vt_conv3x3_destroy(vt_conv3x3 *h) { if (!h) return; (void)hipFree(h->dev ? h->dev : (void *)h->w); delete h; }
 
 // The general form: GroupNorm + ReLU prologue (gn_stats), the convolution to `out` (or NULL), convolution + residual to `fin` (or NULL; res =
 // channels [res_coff, ..) of an NHWC tensor with res_cstride channels), and with stats_ws != NULL the GroupNorm partial sums of the convolution's
@@ -354,8 +350,8 @@ extern "C" int vt_conv3x3_forward_block_stats(const vt_conv3x3 *h, const float *
     double *part = stats_ws ? stats_ws + (size_t)B * stats_groups : nullptr;
     VT_REQUIRE(!fin_stats_ws || (fin && fin_stats_groups > 0), "vt_conv3x3_forward_block_stats: the statistics of the result need the result (fin) and a positive group count");
     double *fpart = fin_stats_ws ? fin_stats_ws + (size_t)B * fin_stats_groups : nullptr;
-    if (h->nt == 2) hipLaunchKernelGGL((conv3x3_kernel<2, true, 0>), grid, dim3(256), 0, vt_stream(stream), in, in_cstride, in_coff, H, W, h->cin, h->w, st2, gamma, beta, groups, out, out_cstride, out_coff, h->inv_scale, h->cout, part, res, res_cstride, res_coff, fin, fin_cstride, fin_coff, nullptr, h->cout, 0, fpart, fin_cstride, fin_coff);
-    else hipLaunchKernelGGL((conv3x3_kernel<1, true, 0>), grid, dim3(256), 0, vt_stream(stream), in, in_cstride, in_coff, H, W, h->cin, h->w, st2, gamma, beta, groups, out, out_cstride, out_coff, h->inv_scale, h->cout, part, res, res_cstride, res_coff, fin, fin_cstride, fin_coff, nullptr, h->cout, 0, fpart, fin_cstride, fin_coff);
+    if (h->nt == 2) hipLaunchKernelGGL((conv3x3_kernel<2, true, 0>), grid, dim3(256), 0, vt_stream(stream), in, in_cstride, in_coff, H, W, h->cin, h->w, st2, gamma, beta, groups, out, out_cstride, out_coff, h->inv_scale, h->cout, part, res, res_cstride, res_coff, fin, fin_cstride, fin_coff, nullptr, h->cout, 0, fpart, fin_cstride, fin_coff, h->scale);
+    else hipLaunchKernelGGL((conv3x3_kernel<1, true, 0>), grid, dim3(256), 0, vt_stream(stream), in, in_cstride, in_coff, H, W, h->cin, h->w, st2, gamma, beta, groups, out, out_cstride, out_coff, h->inv_scale, h->cout, part, res, res_cstride, res_coff, fin, fin_cstride, fin_coff, nullptr, h->cout, 0, fpart, fin_cstride, fin_coff, h->scale);
     VT_LAUNCH_CHECK();
     return VT_OK;
 }
@@ -380,24 +376,18 @@ extern "C" int vt_conv3x3_forward(const vt_conv3x3 *h, const float *in, int B, i
 
 
 // ---- 1 x 1 convolutions (with bias) on the same kernel ------------------------------------------------------------------------------------------
-struct vt_conv1x1 {
-    uint4 *w[2];        // per part of <= 128 output channels: [Cin / 32][4 waves][NT][hi|lo][64 lanes]
-    float *bias;        // (Cout) or NULL
-    int cin, cout, parts, pcout, nt;
-    float inv_scale;
-};
 extern "C" int vt_conv1x1_create(vt_conv1x1 **out, const float *weight, const float *bias, int cout, int cin, void *stream)
 {
     VT_REQUIRE(out && weight && (cout == 64 || cout == 128 || cout == 256) && (cin == 32 || cin == 64 || cin == 128 || cin == 256),
                "vt_conv1x1_create: needs Cout in {64, 128, 256} and Cin in {32, 64, 128, 256}");
     vt_conv1x1 *h = new vt_conv1x1();
     h->cin = cin; h->cout = cout; h->parts = cout == 256 ? 2 : 1; h->pcout = cout / h->parts; h->nt = h->pcout == 128 ? 2 : 1; h->bias = nullptr; h->w[0] = h->w[1] = nullptr;
+    h->scale = nullptr; h->part = nullptr; h->dev = nullptr;
     const int nt = h->nt, nchunk = cin / 32;
     float m = 0.f;
     for (size_t i = 0; i < (size_t)cout * cin; i++) m = fmaxf(m, fabsf(weight[i]));
-    float sw = 1.0f;
-    if (m > 0.f && std::isfinite(m)) { int e; frexpf(m, &e); sw = ldexpf(1.0f, 14 - e); }
-    h->inv_scale = 1.0f / (CV_ACT_SCALE * sw);
+    const float sw = cv_weight_scale(m);
+    h->inv_scale = cv_inv_scale(sw);
     const size_t n16 = (size_t)nchunk * 4 * nt * 2 * 64;
     _Float16 *host = new _Float16[n16 * 8];
     hipStream_t st = vt_stream(stream);
@@ -422,7 +412,13 @@ extern "C" int vt_conv1x1_create(vt_conv1x1 **out, const float *weight, const fl
     *out = h;
     return VT_OK;
 }
-extern "C" void vt_conv1x1_destroy(vt_conv1x1 *h) { if (!h) return; (void)hipFree(h->w[0]); if (h->w[1]) (void)hipFree(h->w[1]); if (h->bias) (void)hipFree(h->bias); delete h; }
+extern "C" void vt_conv1x1_destroy(vt_conv1x1 *h)
+{
+    if (!h) return;
+    if (h->dev) (void)hipFree(h->dev);
+    else { (void)hipFree(h->w[0]); if (h->w[1]) (void)hipFree(h->w[1]); if (h->bias) (void)hipFree(h->bias); }
+    delete h;
+}
 
 extern "C" int vt_conv1x1_forward(const vt_conv1x1 *h, const float *in, int in_cstride, int in_coff, const float *gn_stats, const float *gamma, const float *beta, int groups,
                                   int B, int H, int W, float *out, int out_cstride, int out_coff, const float *res, int res_cstride, int res_coff,
@@ -444,7 +440,7 @@ extern "C" int vt_conv1x1_forward(const vt_conv1x1 *h, const float *in, int in_c
         const float *bs = h->bias ? h->bias + o : nullptr;
 #define CV_L1(NT_, NCH_) hipLaunchKernelGGL((conv3x3_kernel<NT_, false, NCH_>), grid, dim3(256), 0, vt_stream(stream), in, in_cstride, in_coff, H, W, h->cin, h->w[pt], st2, gamma, beta, groups, \
                                           o_plain, out_cstride, out_coff + o, h->inv_scale, h->pcout, res ? nullptr : part, res, res_cstride, res_coff + o, o_fin, out_cstride, out_coff + o, bs, h->cout, o, \
-                                          res ? part : nullptr, h->cout, o)
+                                          res ? part : nullptr, h->cout, o, h->scale)
         const int nch = h->cin / 32;
         if (h->nt == 2) { if (nch == 1) CV_L1(2, 1); else if (nch == 2) CV_L1(2, 2); else if (nch == 4) CV_L1(2, 4); else CV_L1(2, 8); }
         else { if (nch == 1) CV_L1(1, 1); else if (nch == 2) CV_L1(1, 2); else if (nch == 4) CV_L1(1, 4); else CV_L1(1, 8); }

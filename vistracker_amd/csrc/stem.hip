@@ -10,18 +10,12 @@
 //     unit fetches (s_load_dwordx16) for the whole wave -- no vector-memory or LDS traffic for the larger operand at all;
 //   * epilogue through LDS (per wave [64 pixels][33]) so that the NHWC result leaves as 128 contiguous bytes per 8 lanes.
 // Bound: VALU issue (245 x 64 FMAs per pixel, 39 T FMA/s per chip un-packed).
-#include "common.h"
+#include "conv_handles.h"
 
 #define ST_T 16                     /* output tile edge */
 #define ST_P (2 * ST_T + 5)         /* input patch edge: 37 */
 #define ST_PP 40                    /* patch row pitch (floats) */
 #define ST_SP 33                    /* staging pitch per pixel (floats): conflict-free transposition */
-
-struct vt_stem7x7 {
-    float *w;       // [Cin][7][7][Cout]
-    float *bias;    // [Cout] (zeros without one)
-    int cin, cout;
-};
 
 template <int ST_CO>
 __global__ __launch_bounds__(256) void stem7x7_kernel(const float *__restrict__ in, int in_cstride, int in_coff, int Cin, int H, int W, const float *__restrict__ wT,

@@ -355,7 +355,76 @@ class HGFilterEncoder:
         return outputs, tmpx, normx
 
 
-class TrainableConvBlock:
+REPACK_CONV3X3, REPACK_CONV1X1, REPACK_STEM7X7 = 0, 1, 2          # include/vistracker.h: VT_REPACK_*
+_HANDLE_FN = {REPACK_CONV3X3: "vt_conv3x3", REPACK_CONV1X1: "vt_conv1x1", REPACK_STEM7X7: "vt_stem7x7"}
+
+
+class _PackedHandles:
+    """The packed forward handles of a module's convolutions, one per (weight, bias) leaf pair.  A handle is created ONCE, on the device and straight from the leaf
+    (``vt_*_create_device``), and repacked in place (``vt_*_repack``, two launches on the current stream) when a version counter of its pair changed since it was
+    packed: no copy to the host, no synchronisation, no destroy -- the handle's address is stable for the life of the module, and ordering on the stream protects
+    the launches that still read the old packing.  ``EncoderAdam`` repacks all handles of a network in one plan and marks them current, so that the check here
+    finds nothing to do.  An update that goes round the version counters (a kernel writing through ``data_ptr()``, as ``ops.FusedAdam`` does) has to say so with
+    ``invalidate_handles()``.
+
+    ``VT_ENCODER_HOST_REPACK=1`` (``host_repack``) keeps the path this replaced, for A/B: synchronise, destroy the handle, pull the leaf to the host, pack it there
+    with ``vt_*_create`` and copy it back up, per convolution and step."""
+    host_repack = os.environ.get("VT_ENCODER_HOST_REPACK", "0") != "0"
+
+    def _init_handles(self):
+        self._handles = {}          # key -> [handle, (weight version, bias version), kind, weight leaf, bias leaf or None, packed on the host]
+
+    def _packed(self, key, kind, w, b, device):
+        import ctypes as C
+        ent = self._handles.get(key)
+        ver = (w._version, b._version if b is not None else -1)
+        if ent is not None and ent[1] == ver and ent[3] is w and ent[4] is b:
+            return ent[0]
+        lib, fn = L.lib(), _HANDLE_FN[kind]
+        cout, cin = w.shape[:2]
+        bias_arg = kind != REPACK_CONV3X3
+        if ent is not None and (self.host_repack or ent[5]):
+            torch.cuda.synchronize(device)          # launches that read the old packing may still be queued
+            getattr(lib, fn + "_destroy")(ent[0])
+            ent = None
+        with torch.cuda.device(device):
+            if self.host_repack:
+                wh = np.ascontiguousarray(w.detach().cpu().numpy().reshape(cout, cin, -1), np.float32)
+                bh = np.ascontiguousarray(b.detach().cpu().numpy(), np.float32) if b is not None else None
+                h = C.c_void_p()
+                args = (wh.ctypes.data, bh.ctypes.data if bh is not None else None) if bias_arg else (wh.ctypes.data,)
+                L.check(getattr(lib, fn + "_create")(C.byref(h), *args, cout, cin, L.stream_ptr()))
+                ent = [h, ver, kind, w, b, True]
+            else:
+                args = (L.dptr(w.detach()), L.dptr(b.detach()) if b is not None else None) if bias_arg else (L.dptr(w.detach()),)
+                if ent is None:
+                    h = C.c_void_p()
+                    L.check(getattr(lib, fn + "_create_device")(C.byref(h), *args, cout, cin, L.stream_ptr()))
+                    ent = [h, ver, kind, w, b, False]
+                else:
+                    L.check(getattr(lib, fn + "_repack")(ent[0], *args, L.stream_ptr()))
+                    ent[1], ent[3], ent[4] = ver, w, b          # a replaced leaf object is the pair the handle follows from now on
+        self._handles[key] = ent
+        return ent[0]
+
+    def invalidate_handles(self):
+        """the leaves were written behind the version counters: repack every handle at its next use"""
+        for ent in self._handles.values():
+            ent[1] = None
+
+    def _mark_handles_current(self):
+        for ent in self._handles.values():
+            ent[1] = (ent[3]._version, ent[4]._version if ent[4] is not None else -1)
+
+    def __del__(self):
+        try:
+            for ent in getattr(self, "_handles", {}).values():
+                getattr(L.lib(), _HANDLE_FN[ent[2]] + "_destroy")(ent[0])
+        except Exception:
+            pass
+
+
+class TrainableConvBlock(_PackedHandles):
     """One ConvBlock (model/net_util.py:346-396) with its parameters as fp32 device LEAVES under the reference's ``state_dict`` keys, differentiable through
     ``ops.conv_block_train``: the forward is the fused inference forward of ``HGFilterEncoder._conv_block_fused`` bit for bit, the backward one
     ``vt_conv_block_backward`` call (csrc/convtrain.hip).
@@ -364,15 +433,15 @@ class TrainableConvBlock:
         y = blk(x)                      # channels-last (B,Cout,H,W), carries autograd
         y.backward(dy)                  # blk.leaves["conv1.weight"].grad, ..., x.grad
 
-    KNOWN AND NOT DONE: the forward's packed split-f16 convolution handles are rebuilt on the HOST from a leaf whenever its version counter changed (an optimiser
-    step): one device -> host -> device round trip per convolution and step.  A device-side repack is the next row."""
+    The forward's packed split-f16 convolution handles follow the leaves on the device (``_PackedHandles``); ``EncoderAdam`` is the optimiser that keeps a step
+    free of host waits."""
     _W = ("conv1.weight", "conv2.weight", "conv3.weight")
 
     def __init__(self, leaves: dict, device):
         self.device = torch.device(device)
         self.leaves = leaves
         self.has_proj = "downsample.2.weight" in leaves
-        self._handles = {}          # key -> [handle, leaf version it was packed from]
+        self._init_handles()
 
     @classmethod
     def from_state_dict(cls, sd, prefix="", device="cuda:0"):
@@ -417,35 +486,12 @@ class TrainableConvBlock:
         return [lv[k] for k in self._W] + [lv[f"bn{i}.weight"] for i in (1, 2, 3)] + [lv[f"bn{i}.bias"] for i in (1, 2, 3)] + proj
 
     def conv_handles(self, device):
-        """([3 x vt_conv3x3], vt_conv1x1 or None): the packed forward handles, rebuilt from a leaf whose version counter changed since it was packed"""
-        import ctypes as C
-        lib = L.lib()
-        out = []
-        for k in self._W + (("downsample.2.weight",) if self.has_proj else ()):
-            w = self.leaves[k]
-            ent = self._handles.get(k)
-            if ent is None or ent[1] != w._version:
-                if ent is not None:
-                    torch.cuda.synchronize(device)          # launches that read the old packing may still be queued
-                    (lib.vt_conv1x1_destroy if w.shape[2] == 1 else lib.vt_conv3x3_destroy)(ent[0])
-                cout, cin = w.shape[:2]
-                wh = np.ascontiguousarray(w.detach().cpu().numpy().reshape(cout, cin, -1), np.float32)
-                h = C.c_void_p()
-                with torch.cuda.device(device):
-                    if w.shape[2] == 1:
-                        L.check(lib.vt_conv1x1_create(C.byref(h), wh.ctypes.data, None, cout, cin, L.stream_ptr()))
-                    else:
-                        L.check(lib.vt_conv3x3_create(C.byref(h), wh.ctypes.data, cout, cin, L.stream_ptr()))
-                ent = self._handles[k] = [h, w._version]
-            out.append(ent[0])
+        """([3 x vt_conv3x3], vt_conv1x1 or None): the packed forward handles, repacked in place from a leaf whose version counter changed since it was packed"""
+        out = [self._packed(k, REPACK_CONV1X1 if self.leaves[k].shape[2] == 1 else REPACK_CONV3X3, self.leaves[k], None, device)
+               for k in self._W + (("downsample.2.weight",) if self.has_proj else ())]
         return out[:3], (out[3] if self.has_proj else None)
 
-    def __del__(self):
-        try:
-            for k, (h, _) in getattr(self, "_handles", {}).items():
-                (L.lib().vt_conv1x1_destroy if k.startswith("downsample") else L.lib().vt_conv3x3_destroy)(h)
-        except Exception:
-            pass
+    _ensure_handles = conv_handles
 
     def __call__(self, x):
         return ops.conv_block_train(x, self)
@@ -461,10 +507,7 @@ class TrainableHourglass:
         y = hg(x)                       # channels-last (B,features,H,W), carries autograd
         y.backward(dy)                  # hg.blocks["b2_plus_1"].leaves["conv1.weight"].grad, ..., x.grad
 
-    A shape that a block does not serve raises that block's own error (H % 8 == 0 and W % 16 == 0 must still hold at the innermost level).
-
-    KNOWN AND NOT DONE: every block rebuilds its packed forward handles on the HOST after an optimiser step (see ``TrainableConvBlock``): an hourglass of depth 2
-    makes 21 host round trips per step (7 blocks x 3 convolutions) until the device-side repack lands."""
+    A shape that a block does not serve raises that block's own error (H % 8 == 0 and W % 16 == 0 must still hold at the innermost level)."""
 
     def __init__(self, blocks: dict, depth: int, device):
         self.device = torch.device(device)
@@ -508,38 +551,6 @@ def _leaf(v, device):
     return torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).detach().to(device=device, dtype=torch.float32).contiguous().clone().requires_grad_(True)
 
 
-class _PackedHandles:
-    """packed forward handles of (weight, bias) leaf pairs, rebuilt on the HOST from a pair whose version counters changed since it was packed (known and not
-    done: the device-side repack, see ``TrainableConvBlock``)"""
-
-    def _init_handles(self):
-        self._handles = {}          # key -> [handle, (weight version, bias version), destroy]
-
-    def _packed(self, key, w, b, create, destroy, device):
-        import ctypes as C
-        ent = self._handles.get(key)
-        ver = (w._version, b._version)
-        if ent is None or ent[1] != ver:
-            if ent is not None:
-                torch.cuda.synchronize(device)          # launches that read the old packing may still be queued
-                destroy(ent[0])
-            cout, cin = w.shape[:2]
-            wh = np.ascontiguousarray(w.detach().cpu().numpy().reshape(cout, cin, -1), np.float32)
-            bh = np.ascontiguousarray(b.detach().cpu().numpy(), np.float32)
-            h = C.c_void_p()
-            with torch.cuda.device(device):
-                L.check(create(C.byref(h), wh.ctypes.data, bh.ctypes.data, cout, cin, L.stream_ptr()))
-            ent = self._handles[key] = [h, ver, destroy]
-        return ent[0]
-
-    def __del__(self):
-        try:
-            for h, _, destroy in getattr(self, "_handles", {}).values():
-                destroy(h)
-        except Exception:
-            pass
-
-
 class TrainableStem(_PackedHandles):
     """conv1 + bn1 + ReLU (model/HGFilters.py:120-125, 167) with the four parameters as fp32 device leaves under the keys of ``ops.STEM_PARAMS``; differentiable
     through ``ops.stem_train``."""
@@ -556,8 +567,9 @@ class TrainableStem(_PackedHandles):
         return self.tensors()
 
     def handle(self, device):
-        lib = L.lib()
-        return self._packed("conv1", self.leaves["conv1.weight"], self.leaves["conv1.bias"], lib.vt_stem7x7_create, lib.vt_stem7x7_destroy, device)
+        return self._packed("conv1", REPACK_STEM7X7, self.leaves["conv1.weight"], self.leaves["conv1.bias"], device)
+
+    _ensure_handles = handle
 
     def __call__(self, x):
         return ops.stem_train(x, self)
@@ -580,9 +592,10 @@ class TrainableStackTail(_PackedHandles):
         return [t for t in self.tensors() if t is not None]
 
     def handles(self, device):
-        lib = L.lib()
-        return [self._packed(n, self.leaves[n + ".weight"], self.leaves[n + ".bias"], lib.vt_conv1x1_create, lib.vt_conv1x1_destroy, device) if n + ".weight" in self.leaves else None
+        return [self._packed(n, REPACK_CONV1X1, self.leaves[n + ".weight"], self.leaves[n + ".bias"], device) if n + ".weight" in self.leaves else None
                 for n in ("conv_last", "l", "bl", "al")]
+
+    _ensure_handles = handles
 
     def __call__(self, ll, previous=None):
         return ops.stack_tail_train(ll, previous, self, self.last)
@@ -601,8 +614,7 @@ class TrainableHGFilter:
     Serves the image encoder (Cin 5, tmpx 64) and the triplane encoder (Cin 1, tmpx 32).  The input needs H % 32 == 0 and W % 64 == 0 times 2^num_hourglass for
     the innermost level of an hourglass to be a multiple of 8 x 16.
 
-    KNOWN AND NOT DONE: the packed forward handles are rebuilt on the HOST after an optimiser step (see ``TrainableConvBlock``); the device-side repack is the one
-    row of the encoder that remains."""
+    ``EncoderAdam(enc)`` is the optimiser: one Adam launch over all parameters and one two-launch repack of all packed forward handles, no host wait."""
 
     def __init__(self, stem, blocks, hourglasses, tails, num_hourglass, device):
         self.device = torch.device(device)
@@ -677,6 +689,141 @@ class TrainableHGFilter:
                 out, previous = tail(ll, previous)
                 outputs.append(out)
         return outputs, tmpx, normx
+
+
+def _handle_owners(enc):
+    """the modules of a TrainableHGFilter / TrainableHourglass / TrainableConvBlock / TrainableStem / TrainableStackTail that own packed forward handles"""
+    if isinstance(enc, TrainableHGFilter):
+        return [enc.stem] + list(enc.blocks.values()) + [b for hg in enc.hourglasses for b in hg.blocks.values()] + list(enc.tails)
+    if isinstance(enc, TrainableHourglass):
+        return list(enc.blocks.values())
+    if isinstance(enc, _PackedHandles):
+        return [enc]
+    raise TypeError(f"no trainable encoder module: {type(enc).__name__}")
+
+
+def invalidate_handles(enc):
+    """``enc``'s leaves were written behind their version counters (a kernel writing through ``data_ptr()``, as ``ops.FusedAdam`` does): every packed forward
+    handle is repacked at its next use"""
+    for o in _handle_owners(enc):
+        o.invalidate_handles()
+
+
+class EncoderAdam:
+    """Adam (``torch.optim.Adam`` semantics, the arithmetic of ``ops.FusedAdam`` element for element) for a ``TrainableHGFilter``, ``TrainableHourglass`` or
+    ``TrainableConvBlock``, with the whole step on the device:
+
+        opt = EncoderAdam(enc, lr=1e-4)
+        outputs, _, _ = enc(images); loss(outputs).backward()
+        opt.step(); opt.zero_grad()
+
+    * every parameter's ``.data`` is re-homed into ONE flat fp32 buffer (``flat``; each leaf keeps its identity, shape and values, at a 256-byte aligned offset)
+      and its ``.grad`` is bound to a view of one flat gradient buffer (``grad``), into which autograd accumulates in place; ``zero_grad()`` is one memset;
+    * ``m`` and ``v`` are flat too, so ``step()`` is ONE ``vt_adam_step`` launch over everything,
+    * followed by ONE repack plan (``vt_repack_plan_run``: two launches) over all packed forward handles of the module, which are then marked current so that the
+      version check of the next forward does nothing: ``launches_per_step`` = 3 launches and no host wait, whatever the size of the network.
+
+    A leaf whose ``.grad`` was replaced since (set to None and refilled by autograd, or rebound) has its gradient copied into the flat buffer by ``step()`` and
+    is bound again; a leaf WITHOUT a gradient at ``step()`` is skipped as torch and ``ops.FusedAdam`` skip it: its value and its moments are put back after the
+    flat launch (three small copies either side, only when it happens) and its ``.grad`` stays None.  ``state_dict()`` of the module is unchanged.  The plan captures
+    the leaves' addresses: assigning a leaf's ``.data`` afterwards, or putting another tensor in a module's ``leaves``, is an error ``step()`` reports.  Needs the
+    device-side packing (not ``VT_ENCODER_HOST_REPACK``)."""
+
+    def __init__(self, enc, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+        import ctypes as C
+        self.enc, self.lr, self.betas, self.eps, self.t = enc, float(lr), (float(betas[0]), float(betas[1])), float(eps), 0
+        self.device = enc.device
+        self.owners = _handle_owners(enc)
+        if any(o.host_repack for o in self.owners):
+            raise L.VtError("EncoderAdam repacks on the device: it cannot drive handles kept on the host path (VT_ENCODER_HOST_REPACK / host_repack)")
+        self.params = list({id(p): p for p in enc.parameters()}.values())
+        if not self.params or any(not (p.is_cuda and p.dtype == torch.float32 and p.is_leaf) for p in self.params):
+            raise L.VtError("EncoderAdam: the parameters must be fp32 device leaves")
+        offs, total = [], 0
+        for p in self.params:
+            offs.append(total)
+            total += (p.numel() + 63) // 64 * 64
+        self.n, self._offs = total, offs
+        with torch.cuda.device(self.device):
+            self.flat = torch.zeros(total, device=self.device)
+            self.grad = torch.zeros(total, device=self.device)
+            self.m = torch.zeros(total, device=self.device)
+            self.v = torch.zeros(total, device=self.device)
+            self._pviews, self._gviews = [], []
+            for p, o in zip(self.params, offs):
+                pv, gv = self.flat[o:o + p.numel()].view(p.shape), self.grad[o:o + p.numel()].view(p.shape)
+                pv.copy_(p.detach())
+                if p.grad is not None:
+                    gv.copy_(p.grad)
+                p.data = pv
+                p.grad = gv
+                self._pviews.append(pv); self._gviews.append(gv)
+            # every handle packed from the re-homed leaves, then one plan over all of them
+            ents = []
+            for o in self.owners:
+                o.invalidate_handles()
+                o._ensure_handles(self.device)
+                ents += list(o._handles.values())
+            n = len(ents)
+            kinds = (C.c_int * n)(*[e[2] for e in ents])
+            handles = (C.c_void_p * n)(*[e[0].value for e in ents])
+            weights = (C.c_void_p * n)(*[L.dptr(e[3].detach()) for e in ents])
+            biases = (C.c_void_p * n)(*[L.dptr(e[4].detach()) if e[4] is not None else None for e in ents])
+            self._plan = C.c_void_p()
+            L.check(L.lib().vt_repack_plan_create(C.byref(self._plan), n, kinds, handles, weights, biases))
+        self.n_handles, self._planned = n, [(e, e[3], e[4]) for e in ents]
+        self.launches_per_step = 1 + int(L.lib().vt_repack_plan_launches(self._plan))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_plan", None):
+                L.lib().vt_repack_plan_destroy(self._plan)
+        except Exception:
+            pass
+
+    def _bind_grads(self, copy):
+        """bind every leaf's ``.grad`` to its view of the flat buffer; with ``copy`` a replaced gradient is copied in first and a leaf without one is left alone
+        -> the indices of those leaves"""
+        absent = []
+        for i, (p, gv) in enumerate(zip(self.params, self._gviews)):
+            g = p.grad
+            if g is gv or (g is not None and g.data_ptr() == gv.data_ptr() and g.shape == gv.shape and g.is_contiguous()):
+                continue
+            if copy:
+                if g is None:
+                    absent.append(i)
+                    continue
+                gv.copy_(g)
+            p.grad = gv
+        return absent
+
+    def zero_grad(self):
+        """one memset of the flat gradient buffer (and a leaf whose ``.grad`` was replaced is bound to its view again)"""
+        self.grad.zero_()
+        self._bind_grads(copy=False)
+
+    def step(self):
+        for p, pv in zip(self.params, self._pviews):
+            if p.data_ptr() != pv.data_ptr():
+                raise L.VtError("EncoderAdam.step: a parameter's .data was replaced since the optimiser was built; the flat buffer and the repack plan still point at the old storage")
+        for e, w, b in self._planned:
+            if e[3] is not w or e[4] is not b:
+                raise L.VtError("EncoderAdam.step: a leaf of the module was replaced by another tensor since the optimiser was built; the repack plan still reads the old one")
+        absent = self._bind_grads(copy=True)
+        self.t += 1
+        with torch.cuda.device(self.device):
+            # a leaf without a gradient is skipped: whatever the flat launch does to its slice (the gradient slice may hold anything, a NaN included) is undone
+            keep = []
+            for i in absent:
+                sl = slice(self._offs[i], self._offs[i] + self.params[i].numel())
+                keep.append((sl, self.flat[sl].clone(), self.m[sl].clone(), self.v[sl].clone()))
+            L.check(L.lib().vt_adam_step(L.dptr(self.flat), L.dptr(self.grad), L.dptr(self.m), L.dptr(self.v), self.n, self.t, self.lr, self.betas[0], self.betas[1],
+                                         self.eps, None, L.stream_ptr()))
+            for sl, p0, m0, v0 in keep:
+                self.flat[sl].copy_(p0); self.m[sl].copy_(m0); self.v[sl].copy_(v0)
+            L.check(L.lib().vt_repack_plan_run(self._plan, L.stream_ptr()))
+        for o in self.owners:
+            o._mark_handles_current()
 
 
 class SIFNetEncoder:
