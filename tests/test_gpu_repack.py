@@ -326,7 +326,7 @@ def make_module(which, host_repack, monkeypatch):
 
 def handle_addresses(enc):
     from vistracker_amd import encoder as E
-    return [ent[0].value for o in E._handle_owners(enc) for ent in o._handles.values()]
+    return [ent.handle.value for o in E._handle_owners(enc) for ent in o._handles.values()]
 
 
 def reference_steps(which, monkeypatch):
@@ -470,7 +470,7 @@ def test_replaced_leaf_is_followed_and_reported(monkeypatch):
     monkeypatch.setattr(_lib.lib(), "vt_conv3x3_repack", counted)
     with torch.no_grad():
         run(); run()
-    assert len(calls) == 1 and ent[3] is new and enc._handles["conv1.weight"] is ent
+    assert len(calls) == 1 and ent.weight is new and enc._handles["conv1.weight"] is ent
     with pytest.raises(_lib.VtError):
         opt.step()
 

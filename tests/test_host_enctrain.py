@@ -142,3 +142,32 @@ def test_model_matches_the_recorded_reference(tag):
         want = g64[n].reshape(-1)[::EM.GOLDEN_WEIGHT_STEP] if g64[n].ndim == 4 else g64[n]
         err = float(np.abs(v - want).max())
         assert err <= 4 * e32[n] + 1e-30, (n, err, e32[n])
+
+
+def test_stats_hand_over_finalizes_once(monkeypatch):
+    """encoder_fwd.attach_stats / stats_of with the library call stubbed: nothing attached -> None; partial sums are finalized at their first use, with the
+    tensor's own sizes, and never again; an entry attached as finalized is handed over as it is"""
+    from vistracker_amd import _lib, encoder_fwd as fwd
+    calls = []
+
+    class Stub:
+        @staticmethod
+        def vt_groupnorm_finalize(*a):
+            calls.append(a)
+            return 0
+
+    monkeypatch.setattr(_lib, "lib", lambda: Stub)
+    monkeypatch.setattr(_lib, "stream_ptr", lambda: 0)
+    x = torch.zeros(2, 64, 8, 16)
+    assert fwd.stats_of(x) is None and calls == []
+    ws = fwd.partials_workspace(2, 64, 3, "cpu")
+    assert ws.dtype == torch.float64 and ws.numel() == 2 * 32 + 3 * 2 * 64 * 2
+    assert fwd.attach_stats(x, ws, 3) is x
+    assert fwd.stats_of(x) is ws and calls == [(ws.data_ptr(), 3, 2, 8 * 16, 64, 32, 1e-5, 0)]
+    assert fwd.stats_of(x) is ws and len(calls) == 1                    # already finalized: no second launch
+    assert fwd.input_stats(x, True) is ws and len(calls) == 1           # the consumer's way in: the producer's statistics, no pass
+    y = fwd.carry_stats(x, torch.zeros(2, 64, 8, 16))
+    assert fwd.stats_of(y) is ws and len(calls) == 1                    # a copy of x shares the entry, finalized flag included
+    z = fwd.attach_stats(torch.zeros(2, 64, 8, 16), ws, 3, finalized=True)
+    assert fwd.stats_of(z) is ws and len(calls) == 1
+    assert fwd.stats_of(torch.zeros(2, 64, 8, 16)) is None

@@ -21,6 +21,7 @@ Architecture restated from the reference (stacked hourglass, group norm):
 """
 from __future__ import annotations
 
+import dataclasses
 import numpy as np
 import os
 
@@ -28,25 +29,9 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
+from . import encoder_fwd as fwd
 from . import ops
-
-
-def _attach_stats(t, ws, nblk):
-    """the GroupNorm(32) partial sums of ``t`` that its producer left behind (ws: {mean, rstd} area + nblk blocks of partials); finalized on first use"""
-    t._vt_stats = [ws, nblk, False]
-    return t
-
-
-def _stats_of(x):
-    """workspace with the finalized (B, 32) x {mean, rstd} of ``x`` if its producer left the partial sums behind, else None (the consumer runs a pass)"""
-    st = getattr(x, "_vt_stats", None)
-    if st is None:
-        return None
-    if not st[2]:
-        B, C, H, W = x.shape
-        L.check(L.lib().vt_groupnorm_finalize(st[0].data_ptr(), st[1], B, H * W, C, 32, 1e-5, L.stream_ptr()))
-        st[2] = True
-    return st[0]
+from .encoder_fwd import stats_of as _stats_of          # noqa: F401 -- the name the tests know
 
 
 def avgpool2x2(x):
@@ -55,12 +40,7 @@ def avgpool2x2(x):
     B, C, H, W = x.shape
     if not (x.is_cuda and C % 32 == 0 and C <= 1024 and H % 2 == 0 and W % 2 == 0):
         return F.avg_pool2d(x, 2, stride=2)
-    x = x.contiguous(memory_format=torch.channels_last)
-    out = torch.empty(B, C, H // 2, W // 2, device=x.device, memory_format=torch.channels_last)
-    nblk = L.lib().vt_sweep_blocks((H // 2) * (W // 2))
-    ws = torch.empty(B * 32 + nblk * B * C * 2, dtype=torch.float64, device=x.device)
-    L.check(L.lib().vt_avgpool2x2_stats(x.data_ptr(), B, H, W, C, out.data_ptr(), ws.data_ptr(), 32, L.stream_ptr()))
-    return _attach_stats(out, ws, nblk)
+    return fwd.avgpool2x2_stats(x.contiguous(memory_format=torch.channels_last))
 
 
 def upsample2x_bicubic_add(low, skip):
@@ -68,12 +48,9 @@ def upsample2x_bicubic_add(low, skip):
     (``vt_upsample2x_bicubic_add``; torch's channels-last bicubic kernel took 78 % of the encoder time)."""
     B, C, h, w = low.shape
     low = low.contiguous(memory_format=torch.channels_last); skip = skip.contiguous(memory_format=torch.channels_last)
-    out = torch.empty_like(skip, memory_format=torch.channels_last)
     if C % 32 == 0 and C <= 1024:       # + the GroupNorm partial sums of the sum for the ConvBlock that reads it next (top_m / b3)
-        nblk = L.lib().vt_sweep_blocks(4 * h * w)
-        ws = torch.empty(B * 32 + nblk * B * C * 2, dtype=torch.float64, device=low.device)
-        L.check(L.lib().vt_upsample2x_bicubic_add_stats(low.data_ptr(), skip.data_ptr(), B, h, w, C, out.data_ptr(), ws.data_ptr(), 32, L.stream_ptr()))
-        return _attach_stats(out, ws, nblk)
+        return fwd.upsample2x_bicubic_add_stats(low, skip)
+    out = torch.empty_like(skip, memory_format=torch.channels_last)
     L.check(L.lib().vt_upsample2x_bicubic_add(low.data_ptr(), skip.data_ptr(), B, h, w, C, out.data_ptr(), L.stream_ptr()))
     return out
 
@@ -81,15 +58,13 @@ def upsample2x_bicubic_add(low, skip):
 def _gn(x, sd, p, groups=32, relu=False):
     """GroupNorm(32) [+ ReLU]; on the GPU one fused two-pass HIP kernel pair on the channels-last storage (vt_groupnorm_nhwc)"""
     if x.is_cuda and x.shape[1] % 4 == 0:
-        B, C, H, W = x.shape
-        x = x.contiguous(memory_format=torch.channels_last)
-        y = torch.empty_like(x, memory_format=torch.channels_last)
-        ws = torch.empty(L.lib().vt_groupnorm_workspace_doubles(B, H * W, C, groups), dtype=torch.float64, device=x.device)
-        L.check(L.lib().vt_groupnorm_nhwc(x.data_ptr(), sd[p + ".weight"].data_ptr(), sd[p + ".bias"].data_ptr(), B, H * W, C, groups, 1e-5, int(relu),
-                                          ws.data_ptr(), y.data_ptr(), L.stream_ptr()))
-        return y
+        return fwd.groupnorm_relu(x.contiguous(memory_format=torch.channels_last), sd[p + ".weight"], sd[p + ".bias"], groups, relu)[0]
     y = F.group_norm(x, groups, sd[p + ".weight"], sd[p + ".bias"], 1e-5)
     return F.relu(y) if relu else y
+
+
+REPACK_CONV3X3, REPACK_CONV1X1, REPACK_STEM7X7 = 0, 1, 2          # include/vistracker.h: VT_REPACK_*
+_HANDLE_FN = {REPACK_CONV3X3: "vt_conv3x3", REPACK_CONV1X1: "vt_conv1x1", REPACK_STEM7X7: "vt_stem7x7"}
 
 
 class HGFilterEncoder:
@@ -134,86 +109,40 @@ class HGFilterEncoder:
 
     def __del__(self):
         try:
-            for k, h in getattr(self, "_conv_handles", {}).items():
-                (L.lib().vt_conv1x1_destroy if k.startswith("1x1:") else L.lib().vt_stem7x7_destroy if k.startswith("7x7:") else L.lib().vt_conv3x3_destroy)(h)
+            for (kind, _), h in getattr(self, "_conv_handles", {}).items():
+                getattr(L.lib(), _HANDLE_FN[kind] + "_destroy")(h)
         except Exception:
             pass
 
-    def _conv_handle(self, name, device):
+    def _handle(self, kind, wname, bname=None):
+        """the packed forward handle of one convolution, created at its first use: packed on the host (``vt_*_create``) from the NCHW-contiguous copy of the
+        weight (the stored one is channels-last) as (Cout, Cin, ky * k + kx), with the bias ``bname`` if the state dict has it (1 x 1 and stem only)"""
         import ctypes as C
-        h = self._conv_handles.get(name)
+        h = self._conv_handles.get((kind, wname))
         if h is None:
-            w = self.sd[name]; cout, cin = w.shape[:2]
+            w = self.sd[wname]; cout, cin = w.shape[:2]
+            wh = np.ascontiguousarray(w.contiguous().cpu().numpy().reshape(cout, cin, -1), np.float32)
+            args = [wh.ctypes.data]
+            if kind != REPACK_CONV3X3:
+                bh = np.ascontiguousarray(self.sd[bname].cpu().numpy(), np.float32) if bname in self.sd else None
+                args.append(bh.ctypes.data if bh is not None else None)
             h = C.c_void_p()
-            wh = np.ascontiguousarray(w.contiguous().cpu().numpy().reshape(cout, cin, 9), np.float32)          # (Cout, Cin, ky * 3 + kx)
-            with torch.cuda.device(device):
-                L.check(L.lib().vt_conv3x3_create(C.byref(h), wh.ctypes.data, cout, cin, L.stream_ptr()))
-            self._conv_handles[name] = h
+            with torch.cuda.device(self.device):
+                L.check(getattr(L.lib(), _HANDLE_FN[kind] + "_create")(C.byref(h), *args, cout, cin, L.stream_ptr()))
+            self._conv_handles[(kind, wname)] = h
         return h
 
     def _stem(self, x):
         """conv1 (HGFilters.py:118-130, 7 x 7 / stride 2 / pad 3 with bias) -> channels-last (B, 64, ceil(H/2), ceil(W/2))"""
-        import ctypes as C
         w = self.sd["conv1.weight"]; cout, cin = w.shape[:2]
         if not (x.is_cuda and self.use_hip_conv and self.use_hip_stem and cout in (32, 64) and cin <= 8 and tuple(w.shape[2:]) == (7, 7)):
             return self._miopen("stem7x7", x, w, self.sd.get("conv1.bias"), 2, 3)
-        h = self._conv_handles.get("7x7:conv1")
-        if h is None:
-            wh = np.ascontiguousarray(w.contiguous().cpu().numpy().reshape(cout, cin, 49), np.float32)
-            bh = np.ascontiguousarray(self.sd["conv1.bias"].cpu().numpy(), np.float32) if "conv1.bias" in self.sd else None
-            h = C.c_void_p()
-            with torch.cuda.device(x.device):
-                L.check(L.lib().vt_stem7x7_create(C.byref(h), wh.ctypes.data, bh.ctypes.data if bh is not None else None, cout, cin, L.stream_ptr()))
-            self._conv_handles["7x7:conv1"] = h
-        B, _, H, W = x.shape
-        x = x.contiguous(memory_format=torch.channels_last)
-        y = torch.empty(B, cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1, device=x.device, memory_format=torch.channels_last)
         self.routes["hip7x7"] += 1
-        L.check(L.lib().vt_stem7x7_forward(h, x.data_ptr(), cin, 0, B, H, W, y.data_ptr(), cout, 0, L.stream_ptr()))
-        return y
-
-    def _conv1x1_handle(self, wname, bname, device):
-        import ctypes as C
-        h = self._conv_handles.get("1x1:" + wname)
-        if h is None:
-            w = self.sd[wname]; cout, cin = w.shape[:2]
-            wh = np.ascontiguousarray(w.contiguous().cpu().numpy().reshape(cout, cin), np.float32)
-            bh = np.ascontiguousarray(self.sd[bname].cpu().numpy(), np.float32) if bname is not None and bname in self.sd else None
-            h = C.c_void_p()
-            with torch.cuda.device(device):
-                L.check(L.lib().vt_conv1x1_create(C.byref(h), wh.ctypes.data, bh.ctypes.data if bh is not None else None, cout, cin, L.stream_ptr()))
-            self._conv_handles["1x1:" + wname] = h
-        return h
+        return fwd.stem(self._handle(REPACK_STEM7X7, "conv1.weight", "conv1.bias"), x.contiguous(memory_format=torch.channels_last), cout)
 
     def _hip_conv1x1_ok(self, wname, H, W, cuda):
         cout, cin = self.sd[wname].shape[:2]
         return self.use_hip_conv and cuda and cout in (64, 128, 256) and cin in (32, 64, 128, 256) and H % 8 == 0 and W % 16 == 0 and tuple(self.sd[wname].shape[2:]) == (1, 1)
-
-    def _conv1x1(self, x, wname, bname=None, gn=None, res=None, want_stats=False):
-        """1 x 1 convolution (+ bias) of a channels-last tensor on the split-f16 kernel (vt_conv1x1_forward).  ``gn`` = (stats workspace, norm name):
-        GroupNorm(32) + ReLU of the INPUT with those {mean, rstd} pairs, applied while the operand is staged; ``res``: tensor added to the result;
-        ``want_stats``: also return the workspace holding the GroupNorm statistics of the OUTPUT ({mean, rstd} pairs after vt_groupnorm_finalize)."""
-        sd, lib = self.sd, L.lib()
-        B, Cin, H, W = x.shape
-        cout = sd[wname].shape[0]
-        x = x.contiguous(memory_format=torch.channels_last)
-        out = torch.empty(B, cout, H, W, device=x.device, memory_format=torch.channels_last)
-        if res is not None:
-            res = res.contiguous(memory_format=torch.channels_last)
-        ws_out = None
-        if want_stats:
-            tiles = lib.vt_conv3x3_tiles(H, W)
-            ws_out = torch.empty(B * 32 + tiles * B * cout * 2, dtype=torch.float64, device=x.device)
-        self.routes["hip1x1"] += 1
-        L.check(lib.vt_conv1x1_forward(self._conv1x1_handle(wname, bname, x.device), x.data_ptr(), Cin, 0,
-                                       gn[0].data_ptr() if gn else None, sd[gn[1] + ".weight"].data_ptr() if gn else None, sd[gn[1] + ".bias"].data_ptr() if gn else None, 32,
-                                       B, H, W, out.data_ptr(), cout, 0, res.data_ptr() if res is not None else None, cout, 0,
-                                       ws_out.data_ptr() if want_stats else None, 32, L.stream_ptr()))
-        if want_stats:      # of what was written: conv + bias, or conv + bias + res
-            L.check(lib.vt_groupnorm_finalize(ws_out.data_ptr(), tiles, B, H * W, cout, 32, 1e-5, L.stream_ptr()))
-            out._vt_stats = [ws_out, tiles, True]
-            return out, ws_out
-        return out
 
     def _hip_conv_ok(self, name, H, W, cuda):
         cout, cin = self.sd[name].shape[:2]
@@ -254,9 +183,9 @@ class HGFilterEncoder:
                         ws = ws_prev
                         L.check(lib.vt_groupnorm_finalize(ws.data_ptr(), tiles, B, H * W, C, 32, 1e-5, L.stream_ptr()))
                     nxt = i < 3 and self._hip_conv_ok(p + f"conv{i + 1}.weight", H, W, True)
-                    ws_out = torch.empty(B * 32 + tiles * B * co * 2, dtype=torch.float64, device=x.device) if nxt else None
+                    ws_out = fwd.partials_workspace(B, co, tiles, x.device) if nxt else None
                     self.routes["hip3x3"] += 1
-                    L.check(lib.vt_conv3x3_forward_gn_stats(self._conv_handle(wn, x.device), src.data_ptr(), cstride, coff, ws.data_ptr(),
+                    L.check(lib.vt_conv3x3_forward_gn_stats(self._handle(REPACK_CONV3X3, wn), src.data_ptr(), cstride, coff, ws.data_ptr(),
                                                             sd[gn + ".weight"].data_ptr(), sd[gn + ".bias"].data_ptr(), 32, B, H, W, out.data_ptr(), Ct, off,
                                                             ws_out.data_ptr() if nxt else None, 32, L.stream_ptr()))
                     ws_prev = ws_out
@@ -273,44 +202,25 @@ class HGFilterEncoder:
         return out + x
 
     def _conv_block_fused(self, x, p, couts):
-        """all three convolutions on the split-f16 kernel: GroupNorm + ReLU in the operand staging, the statistics of the inner convolutions from the
-        per-tile partial sums of their producer, and the block's result (concatenation + residual, model/net_util.py:390-394) written by the
-        convolutions themselves: ``raw`` holds o1 | o2 for the next convolution to read, ``fin`` = cat(o1, o2, o3) + residual"""
-        sd, lib = self.sd, L.lib()
-        B, Cin, H, W = x.shape
+        """all three convolutions on the split-f16 kernel (``encoder_fwd.conv_block``): GroupNorm + ReLU in the operand staging, the block's result
+        (concatenation + residual, model/net_util.py:390-394) written by the convolutions themselves; the residual is ``x`` or its 1 x 1 projection"""
+        sd = self.sd
+        H, W = x.shape[2:]
         x = x.contiguous(memory_format=torch.channels_last)
-        Ct, Cr = sum(couts), couts[0] + couts[1]
-        tiles = lib.vt_conv3x3_tiles(H, W)
-        ws = _stats_of(x) if self.producer_stats else None      # left behind by the producer of x (previous block, pooling, up-sampling, 1 x 1 sum)
-        if ws is None:
-            ws = torch.empty(lib.vt_groupnorm_workspace_doubles(B, H * W, Cin, 32), dtype=torch.float64, device=x.device)
-            L.check(lib.vt_groupnorm_stats(x.data_ptr(), Cin, 0, B, H * W, Cin, 32, 1e-5, ws.data_ptr(), L.stream_ptr()))
-        res = x
-        if p + "downsample.2.weight" in sd:         # see _conv_block: Sequential(bn4, ReLU, conv1x1)
-            if self._hip_conv1x1_ok(p + "downsample.2.weight", H, W, True):
+        Ct = sum(couts)
+        ws = fwd.input_stats(x, self.producer_stats)      # left behind by the producer of x (previous block, pooling, up-sampling, 1 x 1 sum), else one pass
+        res, wp = x, p + "downsample.2.weight"
+        if wp in sd:         # see _conv_block: Sequential(bn4, ReLU, conv1x1)
+            if self._hip_conv1x1_ok(wp, H, W, True):
                 # the projection's GroupNorm normalises the same tensor as bn1: same {mean, rstd}, its own gamma / beta, fused into the staging
-                res = self._conv1x1(x, p + "downsample.2.weight", None, gn=(ws, p + "downsample.0"))
+                self.routes["hip1x1"] += 1
+                res, _ = fwd.conv1x1(self._handle(REPACK_CONV1X1, wp), x, sd[wp].shape[0], gn=(ws, sd[p + "downsample.0.weight"], sd[p + "downsample.0.bias"]))
             else:
-                res = self._miopen(p + "downsample", _gn(x, sd, p + "downsample.0", relu=True), sd[p + "downsample.2.weight"]).contiguous(memory_format=torch.channels_last)
+                res = self._miopen(p + "downsample", _gn(x, sd, p + "downsample.0", relu=True), sd[wp]).contiguous(memory_format=torch.channels_last)
         assert res.shape[1] == Ct
-        raw = torch.empty(B, Cr, H, W, device=x.device, memory_format=torch.channels_last)
-        fin = torch.empty(B, Ct, H, W, device=x.device, memory_format=torch.channels_last)
-        src, cstride, coff, C, off = x, Cin, 0, Cin, 0
-        ws_fin = torch.empty(B * 32 + tiles * B * Ct * 2, dtype=torch.float64, device=x.device) if (self.producer_stats and Ct % 32 == 0) else None
-        for i, co in zip((1, 2, 3), couts):
-            wn, gn = p + f"conv{i}.weight", p + f"bn{i}"
-            ws_out = torch.empty(B * 32 + tiles * B * co * 2, dtype=torch.float64, device=x.device) if i < 3 else None
-            self.routes["hip3x3"] += 1
-            L.check(lib.vt_conv3x3_forward_block_stats(self._conv_handle(wn, x.device), src.data_ptr(), cstride, coff, ws.data_ptr(), sd[gn + ".weight"].data_ptr(),
-                                                       sd[gn + ".bias"].data_ptr(), 32, B, H, W, raw.data_ptr() if i < 3 else None, Cr, off if i < 3 else 0,
-                                                       res.data_ptr(), Ct, off, fin.data_ptr(), Ct, off, ws_out.data_ptr() if i < 3 else None, 32,
-                                                       ws_fin.data_ptr() if ws_fin is not None else None, 32, L.stream_ptr()))
-            if i < 3:
-                L.check(lib.vt_groupnorm_finalize(ws_out.data_ptr(), tiles, B, H * W, co, 32, 1e-5, L.stream_ptr()))
-                ws = ws_out
-            src, cstride, coff, C = raw, Cr, off, co
-            off += co
-        return _attach_stats(fin, ws_fin, tiles) if ws_fin is not None else fin
+        self.routes["hip3x3"] += 3
+        return fwd.conv_block([self._handle(REPACK_CONV3X3, p + f"conv{i}.weight") for i in (1, 2, 3)], [sd[p + f"bn{i}.weight"] for i in (1, 2, 3)],
+                              [sd[p + f"bn{i}.bias"] for i in (1, 2, 3)], x, ws, res, couts, self.producer_stats and Ct % 32 == 0)[0]
 
     def _hourglass(self, level, x, p):
         up1 = self._conv_block(x, f"{p}b1_{level}.")
@@ -336,27 +246,34 @@ class HGFilterEncoder:
         for i in range(self.num_stack):
             ll = self._conv_block(self._hourglass(self.depth, previous, f"m{i}."), f"top_m_{i}.")
             H, W = ll.shape[2:]
-            names = [f"conv_last{i}.weight", f"l{i}.weight"] + ([f"bl{i}.weight", f"al{i}.weight"] if i < self.num_stack - 1 else [])
+            last = i == self.num_stack - 1
+            names = [f"conv_last{i}.weight", f"l{i}.weight"] + ([] if last else [f"bl{i}.weight", f"al{i}.weight"])
             if ll.is_cuda and all(self._hip_conv1x1_ok(n, H, W, True) for n in names):
-                # the tail of a stack as four launches of the 1 x 1 kernel: conv_last leaves the statistics of its output behind, bn_end + ReLU is
-                # applied in the operand staging of its two consumers (l, bl), and `previous + bl(ll) + al(out)` is the residual input of bl and al
-                raw, ws = self._conv1x1(ll, f"conv_last{i}.weight", f"conv_last{i}.bias", want_stats=True)
-                out = self._conv1x1(raw, f"l{i}.weight", f"l{i}.bias", gn=(ws, f"bn_end{i}"))
+                # the tail of a stack as four launches of the 1 x 1 kernel (two on the last stack)
+                handles = [self._handle(REPACK_CONV1X1, n, n[:-6] + "bias") for n in names] + [None] * (4 - len(names))
+                self.routes["hip1x1"] += len(names)
+                ll, previous = (t.contiguous(memory_format=torch.channels_last) for t in (ll, previous))
+                _, _, out, nxt, _ = fwd.stack_tail(handles, sd[f"bn_end{i}.weight"], sd[f"bn_end{i}.bias"], ll, previous, sd[f"l{i}.weight"].shape[0], last)
                 outputs.append(out)
-                if i < self.num_stack - 1:
-                    tmp = self._conv1x1(raw, f"bl{i}.weight", f"bl{i}.bias", gn=(ws, f"bn_end{i}"), res=previous)
-                    previous, _ = self._conv1x1(out, f"al{i}.weight", f"al{i}.bias", res=tmp, want_stats=True)      # the next stack's b1 normalises it
+                previous = previous if last else nxt
                 continue
             ll = _gn(self._miopen(f"conv_last{i}", ll, sd[f"conv_last{i}.weight"], sd[f"conv_last{i}.bias"]), sd, f"bn_end{i}", relu=True)
             out = self._miopen(f"l{i}", ll, sd[f"l{i}.weight"], sd[f"l{i}.bias"])
             outputs.append(out)
-            if i < self.num_stack - 1:
+            if not last:
                 previous = previous + self._miopen(f"bl{i}", ll, sd[f"bl{i}.weight"], sd[f"bl{i}.bias"]) + self._miopen(f"al{i}", out, sd[f"al{i}.weight"], sd[f"al{i}.bias"])
         return outputs, tmpx, normx
 
 
-REPACK_CONV3X3, REPACK_CONV1X1, REPACK_STEM7X7 = 0, 1, 2          # include/vistracker.h: VT_REPACK_*
-_HANDLE_FN = {REPACK_CONV3X3: "vt_conv3x3", REPACK_CONV1X1: "vt_conv1x1", REPACK_STEM7X7: "vt_stem7x7"}
+@dataclasses.dataclass(eq=False, slots=True)
+class _Packed:
+    """one packed forward handle and the leaf pair it was packed from"""
+    handle: object          # ctypes.c_void_p
+    version: object         # (weight version, bias version) when it was packed; None = repack at the next use
+    kind: int               # REPACK_*
+    weight: torch.Tensor
+    bias: object            # leaf or None
+    on_host: bool           # packed on the host (vt_*_create): replaced, not repacked in place
 
 
 class _PackedHandles:
@@ -372,20 +289,20 @@ class _PackedHandles:
     host_repack = os.environ.get("VT_ENCODER_HOST_REPACK", "0") != "0"
 
     def _init_handles(self):
-        self._handles = {}          # key -> [handle, (weight version, bias version), kind, weight leaf, bias leaf or None, packed on the host]
+        self._handles = {}          # key -> _Packed
 
     def _packed(self, key, kind, w, b, device):
         import ctypes as C
         ent = self._handles.get(key)
         ver = (w._version, b._version if b is not None else -1)
-        if ent is not None and ent[1] == ver and ent[3] is w and ent[4] is b:
-            return ent[0]
+        if ent is not None and ent.version == ver and ent.weight is w and ent.bias is b:
+            return ent.handle
         lib, fn = L.lib(), _HANDLE_FN[kind]
         cout, cin = w.shape[:2]
         bias_arg = kind != REPACK_CONV3X3
-        if ent is not None and (self.host_repack or ent[5]):
+        if ent is not None and (self.host_repack or ent.on_host):
             torch.cuda.synchronize(device)          # launches that read the old packing may still be queued
-            getattr(lib, fn + "_destroy")(ent[0])
+            getattr(lib, fn + "_destroy")(ent.handle)
             ent = None
         with torch.cuda.device(device):
             if self.host_repack:
@@ -394,39 +311,39 @@ class _PackedHandles:
                 h = C.c_void_p()
                 args = (wh.ctypes.data, bh.ctypes.data if bh is not None else None) if bias_arg else (wh.ctypes.data,)
                 L.check(getattr(lib, fn + "_create")(C.byref(h), *args, cout, cin, L.stream_ptr()))
-                ent = [h, ver, kind, w, b, True]
+                ent = _Packed(h, ver, kind, w, b, True)
             else:
                 args = (L.dptr(w.detach()), L.dptr(b.detach()) if b is not None else None) if bias_arg else (L.dptr(w.detach()),)
                 if ent is None:
                     h = C.c_void_p()
                     L.check(getattr(lib, fn + "_create_device")(C.byref(h), *args, cout, cin, L.stream_ptr()))
-                    ent = [h, ver, kind, w, b, False]
+                    ent = _Packed(h, ver, kind, w, b, False)
                 else:
-                    L.check(getattr(lib, fn + "_repack")(ent[0], *args, L.stream_ptr()))
-                    ent[1], ent[3], ent[4] = ver, w, b          # a replaced leaf object is the pair the handle follows from now on
+                    L.check(getattr(lib, fn + "_repack")(ent.handle, *args, L.stream_ptr()))
+                    ent.version, ent.weight, ent.bias = ver, w, b          # a replaced leaf object is the pair the handle follows from now on
         self._handles[key] = ent
-        return ent[0]
+        return ent.handle
 
     def invalidate_handles(self):
         """the leaves were written behind the version counters: repack every handle at its next use"""
         for ent in self._handles.values():
-            ent[1] = None
+            ent.version = None
 
     def _mark_handles_current(self):
         for ent in self._handles.values():
-            ent[1] = (ent[3]._version, ent[4]._version if ent[4] is not None else -1)
+            ent.version = (ent.weight._version, ent.bias._version if ent.bias is not None else -1)
 
     def __del__(self):
         try:
             for ent in getattr(self, "_handles", {}).values():
-                getattr(L.lib(), _HANDLE_FN[ent[2]] + "_destroy")(ent[0])
+                getattr(L.lib(), _HANDLE_FN[ent.kind] + "_destroy")(ent.handle)
         except Exception:
             pass
 
 
 class TrainableConvBlock(_PackedHandles):
     """One ConvBlock (model/net_util.py:346-396) with its parameters as fp32 device LEAVES under the reference's ``state_dict`` keys, differentiable through
-    ``ops.conv_block_train``: the forward is the fused inference forward of ``HGFilterEncoder._conv_block_fused`` bit for bit, the backward one
+    ``ops.conv_block_train``: the forward is the fused inference forward bit for bit (both call ``encoder_fwd.conv_block``), the backward one
     ``vt_conv_block_backward`` call (csrc/convtrain.hip).
 
         blk = TrainableConvBlock.from_state_dict(sd, "image_filter.conv3.")
@@ -485,13 +402,11 @@ class TrainableConvBlock(_PackedHandles):
         proj = [lv["downsample.2.weight"], lv["bn4.weight"], lv["bn4.bias"]] if self.has_proj else [None, None, None]
         return [lv[k] for k in self._W] + [lv[f"bn{i}.weight"] for i in (1, 2, 3)] + [lv[f"bn{i}.bias"] for i in (1, 2, 3)] + proj
 
-    def conv_handles(self, device):
+    def handles(self, device):
         """([3 x vt_conv3x3], vt_conv1x1 or None): the packed forward handles, repacked in place from a leaf whose version counter changed since it was packed"""
         out = [self._packed(k, REPACK_CONV1X1 if self.leaves[k].shape[2] == 1 else REPACK_CONV3X3, self.leaves[k], None, device)
                for k in self._W + (("downsample.2.weight",) if self.has_proj else ())]
         return out[:3], (out[3] if self.has_proj else None)
-
-    _ensure_handles = conv_handles
 
     def __call__(self, x):
         return ops.conv_block_train(x, self)
@@ -566,10 +481,9 @@ class TrainableStem(_PackedHandles):
     def parameters(self):
         return self.tensors()
 
-    def handle(self, device):
+    def handles(self, device):
+        """the packed vt_stem7x7 forward handle"""
         return self._packed("conv1", REPACK_STEM7X7, self.leaves["conv1.weight"], self.leaves["conv1.bias"], device)
-
-    _ensure_handles = handle
 
     def __call__(self, x):
         return ops.stem_train(x, self)
@@ -592,10 +506,9 @@ class TrainableStackTail(_PackedHandles):
         return [t for t in self.tensors() if t is not None]
 
     def handles(self, device):
+        """[conv_last, l, bl, al]: the packed vt_conv1x1 forward handles (bl and al None on the last stack)"""
         return [self._packed(n, REPACK_CONV1X1, self.leaves[n + ".weight"], self.leaves[n + ".bias"], device) if n + ".weight" in self.leaves else None
                 for n in ("conv_last", "l", "bl", "al")]
-
-    _ensure_handles = handles
 
     def __call__(self, ll, previous=None):
         return ops.stack_tail_train(ll, previous, self, self.last)
@@ -603,7 +516,7 @@ class TrainableStackTail(_PackedHandles):
 
 class TrainableHGFilter:
     """The reference's ``HGFilter`` (model/HGFilters.py:56-203; norm='group', hg_down='ave_pool') that trains: every parameter an fp32 device leaf, the forward
-    the launches of ``HGFilterEncoder.__call__`` bit for bit, the backward entirely on the library's kernels.  Built from a ``TrainableStem`` (``.stem``),
+    the launches of ``HGFilterEncoder.__call__`` bit for bit (both sides issue them through ``encoder_fwd``), the backward entirely on the library's kernels.  Built from a ``TrainableStem`` (``.stem``),
     ``TrainableConvBlock``s (``.blocks``: 'conv2', 'conv3', 'conv4', 'top_m_i'), ``TrainableHourglass``es (``.hourglasses[i]`` = m_i) and ``TrainableStackTail``s
     (``.tails[i]``), joined by ``ops.avgpool2x2_train``.
 
@@ -762,16 +675,16 @@ class EncoderAdam:
             ents = []
             for o in self.owners:
                 o.invalidate_handles()
-                o._ensure_handles(self.device)
+                o.handles(self.device)
                 ents += list(o._handles.values())
             n = len(ents)
-            kinds = (C.c_int * n)(*[e[2] for e in ents])
-            handles = (C.c_void_p * n)(*[e[0].value for e in ents])
-            weights = (C.c_void_p * n)(*[L.dptr(e[3].detach()) for e in ents])
-            biases = (C.c_void_p * n)(*[L.dptr(e[4].detach()) if e[4] is not None else None for e in ents])
+            kinds = (C.c_int * n)(*[e.kind for e in ents])
+            handles = (C.c_void_p * n)(*[e.handle.value for e in ents])
+            weights = (C.c_void_p * n)(*[L.dptr(e.weight.detach()) for e in ents])
+            biases = (C.c_void_p * n)(*[L.dptr(e.bias.detach()) if e.bias is not None else None for e in ents])
             self._plan = C.c_void_p()
             L.check(L.lib().vt_repack_plan_create(C.byref(self._plan), n, kinds, handles, weights, biases))
-        self.n_handles, self._planned = n, [(e, e[3], e[4]) for e in ents]
+        self.n_handles, self._planned = n, [(e, e.weight, e.bias) for e in ents]
         self.launches_per_step = 1 + int(L.lib().vt_repack_plan_launches(self._plan))
 
     def __del__(self):
@@ -807,7 +720,7 @@ class EncoderAdam:
             if p.data_ptr() != pv.data_ptr():
                 raise L.VtError("EncoderAdam.step: a parameter's .data was replaced since the optimiser was built; the flat buffer and the repack plan still point at the old storage")
         for e, w, b in self._planned:
-            if e[3] is not w or e[4] is not b:
+            if e.weight is not w or e.bias is not b:
                 raise L.VtError("EncoderAdam.step: a leaf of the module was replaced by another tensor since the optimiser was built; the repack plan still reads the old one")
         absent = self._bind_grads(copy=True)
         self.t += 1

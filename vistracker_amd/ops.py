@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import encoder_fwd as fwd
 
 
 def _f32(t):
@@ -895,46 +896,14 @@ def conv_block_backward_raw(dy, x, raw, stats, params, want=None, out=None, accu
 class _ConvBlockTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, blk, x, *tensors):
-        # the launches of HGFilterEncoder._conv_block_fused (encoder.py), keeping what the backward reads: x, raw = o1 | o2 and the three {mean, rstd} areas
-        lib = L.lib()
+        # the fused block of encoder_fwd, keeping what the backward reads: x, raw = o1 | o2 and the three {mean, rstd} areas
         p = dict(zip(CONV_BLOCK_PARAMS, tensors))
-        B, Cin, H, W = x.shape
         couts = [int(p[k].shape[0]) for k in ("w1", "w2", "w3")]
-        Ct, Cr = sum(couts), couts[0] + couts[1]
         with torch.cuda.device(x.device):
-            h3, h1 = blk.conv_handles(x.device)
-            tiles = lib.vt_conv3x3_tiles(H, W)
-            st = getattr(x, "_vt_stats", None)          # left behind by the producer of x (a previous block): finalized on first use, as encoder._stats_of
-            if st is not None:
-                if not st[2]:
-                    L.check(lib.vt_groupnorm_finalize(st[0].data_ptr(), st[1], B, H * W, Cin, 32, 1e-5, L.stream_ptr()))
-                    st[2] = True
-                ws = st[0]
-            else:
-                ws = torch.empty(lib.vt_groupnorm_workspace_doubles(B, H * W, Cin, 32), dtype=torch.float64, device=x.device)
-                L.check(lib.vt_groupnorm_stats(x.data_ptr(), Cin, 0, B, H * W, Cin, 32, 1e-5, ws.data_ptr(), L.stream_ptr()))
-            res = x
-            if h1 is not None:
-                res = torch.empty(B, Ct, H, W, device=x.device, memory_format=torch.channels_last)
-                L.check(lib.vt_conv1x1_forward(h1, x.data_ptr(), Cin, 0, ws.data_ptr(), p["gamma4"].data_ptr(), p["beta4"].data_ptr(), 32, B, H, W,
-                                               res.data_ptr(), Ct, 0, None, Ct, 0, None, 32, L.stream_ptr()))
-            raw = torch.empty(B, Cr, H, W, device=x.device, memory_format=torch.channels_last)
-            fin = torch.empty(B, Ct, H, W, device=x.device, memory_format=torch.channels_last)
-            ws_fin = torch.empty(B * 32 + tiles * B * Ct * 2, dtype=torch.float64, device=x.device)
-            src, cstride, coff, off = x, Cin, 0, 0
-            stats = [ws]
-            for i, co in enumerate(couts):
-                last = i == 2
-                ws_out = None if last else torch.empty(B * 32 + tiles * B * co * 2, dtype=torch.float64, device=x.device)
-                L.check(lib.vt_conv3x3_forward_block_stats(h3[i], src.data_ptr(), cstride, coff, stats[-1].data_ptr(), p[f"gamma{i + 1}"].data_ptr(),
-                                                           p[f"beta{i + 1}"].data_ptr(), 32, B, H, W, None if last else raw.data_ptr(), Cr, 0 if last else off,
-                                                           res.data_ptr(), Ct, off, fin.data_ptr(), Ct, off, None if last else ws_out.data_ptr(), 32,
-                                                           ws_fin.data_ptr(), 32, L.stream_ptr()))
-                if not last:
-                    L.check(lib.vt_groupnorm_finalize(ws_out.data_ptr(), tiles, B, H * W, co, 32, 1e-5, L.stream_ptr()))
-                    stats.append(ws_out)
-                src, cstride, coff = raw, Cr, off
-                off += co
+            h3, h1 = blk.handles(x.device)
+            ws = fwd.input_stats(x, True)           # left behind by the producer of x (a previous block), else one pass
+            res = x if h1 is None else fwd.conv1x1(h1, x, sum(couts), gn=(ws, p["gamma4"], p["beta4"]))[0]
+            fin, raw, stats, ws_fin = fwd.conv_block(h3, [p[f"gamma{i}"] for i in (1, 2, 3)], [p[f"beta{i}"] for i in (1, 2, 3)], x, ws, res, couts, True)
         ctx.save_for_backward(x, raw, *stats, *[t for t in tensors if t is not None])
         ctx.present = [t is not None for t in tensors]
         ctx.mark_non_differentiable(ws_fin)
@@ -958,8 +927,8 @@ class _ConvBlockTrainFn(torch.autograd.Function):
 
 def conv_block_train(x, params):
     """A ConvBlock (model/net_util.py:346-396) that a torch graph can contain.  ``x``: (B,Cin,H,W) device tensor (kept channels-last); ``params``: an
-    ``encoder.TrainableConvBlock`` (its leaves ``tensors()`` in CONV_BLOCK_PARAMS order and the packed forward handles ``conv_handles(device)``).  Forward:
-    exactly the fused inference forward (the launches of ``HGFilterEncoder._conv_block_fused``); backward: one ``vt_conv_block_backward`` call, a gradient for
+    ``encoder.TrainableConvBlock`` (its leaves ``tensors()`` in CONV_BLOCK_PARAMS order and the packed forward handles ``handles(device)``).  Forward:
+    exactly the fused inference forward (``encoder_fwd.conv_block``, the launches ``HGFilterEncoder._conv_block_fused`` issues); backward: one ``vt_conv_block_backward`` call, a gradient for
     every input that requires one.  The result carries the GroupNorm partial sums of itself for a block that reads it next, as the inference path does."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
         raise L.VtError("conv_block_train: x must be a (B,C,H,W) device tensor; there is no CPU path")
@@ -968,12 +937,9 @@ def conv_block_train(x, params):
     couts = [int(tensors[i].shape[0]) for i in range(3)]
     if int(L.lib().vt_conv_block_backward_workspace(B, H, W, Cin, *couts)) < 0 or int(tensors[0].shape[1]) != Cin or (tensors[9] is None) != (Cin == sum(couts)):
         raise L.VtError(f"conv_block_train: block {Cin}->{couts} at {H}x{W} is not served (H % 8 == 0, W % 16 == 0, widths in {{32, 64, 128}}, Cin % 32 == 0 up to 256)")
-    xc = x if x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last) else x.float().contiguous(memory_format=torch.channels_last)
-    if xc is not x and hasattr(x, "_vt_stats"):
-        xc._vt_stats = x._vt_stats
+    xc = x if x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last) else fwd.carry_stats(x, x.float().contiguous(memory_format=torch.channels_last))
     fin, ws_fin = _ConvBlockTrainFn.apply(params, xc, *tensors)
-    fin._vt_stats = [ws_fin, int(L.lib().vt_conv3x3_tiles(H, W)), False]
-    return fin
+    return fwd.attach_stats(fin, ws_fin, int(L.lib().vt_conv3x3_tiles(H, W)))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1011,13 +977,9 @@ def upsample2x_bicubic_backward(d_out):
 class _AvgPoolTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        # the launch of encoder.avgpool2x2: the pooled tensor + the GroupNorm partial sums of it
-        B, C, H, W = x.shape
-        out = torch.empty(B, C, H // 2, W // 2, device=x.device, memory_format=torch.channels_last)
-        nblk = L.lib().vt_sweep_blocks((H // 2) * (W // 2))
-        ws = torch.empty(B * 32 + nblk * B * C * 2, dtype=torch.float64, device=x.device)
         with torch.cuda.device(x.device):
-            L.check(L.lib().vt_avgpool2x2_stats(x.data_ptr(), B, H, W, C, out.data_ptr(), ws.data_ptr(), 32, L.stream_ptr()))
+            out = fwd.avgpool2x2_stats(x)
+        ws, _ = fwd.partials_of(out)
         ctx.mark_non_differentiable(ws)
         return out, ws
 
@@ -1029,13 +991,9 @@ class _AvgPoolTrainFn(torch.autograd.Function):
 class _UpsampleAddTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, low, skip):
-        # the launch of encoder.upsample2x_bicubic_add: skip + up(low) + the GroupNorm partial sums of the sum
-        B, C, h, w = low.shape
-        out = torch.empty_like(skip, memory_format=torch.channels_last)
-        nblk = L.lib().vt_sweep_blocks(4 * h * w)
-        ws = torch.empty(B * 32 + nblk * B * C * 2, dtype=torch.float64, device=low.device)
         with torch.cuda.device(low.device):
-            L.check(L.lib().vt_upsample2x_bicubic_add_stats(low.data_ptr(), skip.data_ptr(), B, h, w, C, out.data_ptr(), ws.data_ptr(), 32, L.stream_ptr()))
+            out = fwd.upsample2x_bicubic_add_stats(low, skip)
+        ws, _ = fwd.partials_of(out)
         ctx.mark_non_differentiable(ws)
         return out, ws
 
@@ -1046,20 +1004,19 @@ class _UpsampleAddTrainFn(torch.autograd.Function):
 
 
 def avgpool2x2_train(x):
-    """``F.avg_pool2d(x, 2, stride=2)`` that a torch graph can contain.  Forward: the inference launch (``encoder.avgpool2x2``, vt_avgpool2x2_stats) bit for
+    """``F.avg_pool2d(x, 2, stride=2)`` that a torch graph can contain.  Forward: the inference launch (``encoder_fwd.avgpool2x2_stats``) bit for
     bit, the result carrying the GroupNorm partial sums of itself for the block that reads it next; backward: one ``vt_avgpool2x2_backward`` call."""
     xc = _resample_arg("avgpool2x2_train", x)
     B, C, H, W = xc.shape
     if C % 32 or C > 1024 or H % 2 or W % 2 or H < 2 or W < 2:
         raise L.VtError(f"avgpool2x2_train: {C} channels at {H}x{W} is not served (C % 32 == 0 up to 1024, even H and W)")
     out, ws = _AvgPoolTrainFn.apply(xc)
-    out._vt_stats = [ws, int(L.lib().vt_sweep_blocks((H // 2) * (W // 2))), False]
-    return out
+    return fwd.attach_stats(out, ws, int(L.lib().vt_sweep_blocks((H // 2) * (W // 2))))
 
 
 def upsample2x_bicubic_add_train(low, skip):
     """``skip + F.interpolate(low, scale_factor=2, mode='bicubic', align_corners=True)`` that a torch graph can contain.  Forward: the inference launch
-    (``encoder.upsample2x_bicubic_add``, vt_upsample2x_bicubic_add_stats) bit for bit, with the GroupNorm partial sums of the result attached; backward: one
+    (``encoder_fwd.upsample2x_bicubic_add_stats``) bit for bit, with the GroupNorm partial sums of the result attached; backward: one
     ``vt_upsample2x_bicubic_backward`` call for ``low``, the upstream gradient itself for ``skip``."""
     lc, sc = _resample_arg("upsample2x_bicubic_add_train", low), _resample_arg("upsample2x_bicubic_add_train", skip)
     B, C, h, w = lc.shape
@@ -1068,8 +1025,7 @@ def upsample2x_bicubic_add_train(low, skip):
     if C % 32 or C > 1024:
         raise L.VtError(f"upsample2x_bicubic_add_train: {C} channels is not served (C % 32 == 0 up to 1024)")
     out, ws = _UpsampleAddTrainFn.apply(lc, sc)
-    out._vt_stats = [ws, int(L.lib().vt_sweep_blocks(4 * h * w)), False]
-    return out
+    return fwd.attach_stats(out, ws, int(L.lib().vt_sweep_blocks(4 * h * w)))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1159,17 +1115,10 @@ def stack_tail_backward_raw(d_out, d_prev, ll, raw, out, stats, params, want=Non
 class _StemTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mod, x, w, b, gamma, beta):
-        # the launches of HGFilterEncoder._stem + _gn(..., relu=True) (encoder.py), keeping what the backward reads: x, conv1's output, tmpx, the {mean, rstd} area
-        lib = L.lib()
-        B, cin, H, W = x.shape
-        cout = int(w.shape[0])
+        # stem + GroupNorm / ReLU of encoder_fwd, keeping what the backward reads: x, conv1's output, tmpx, the {mean, rstd} area
         with torch.cuda.device(x.device):
-            y1 = torch.empty(B, cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1, device=x.device, memory_format=torch.channels_last)
-            L.check(lib.vt_stem7x7_forward(mod.handle(x.device), x.data_ptr(), cin, 0, B, H, W, y1.data_ptr(), cout, 0, L.stream_ptr()))
-            HW = y1.shape[2] * y1.shape[3]
-            y = torch.empty_like(y1, memory_format=torch.channels_last)
-            ws = torch.empty(lib.vt_groupnorm_workspace_doubles(B, HW, cout, 32), dtype=torch.float64, device=x.device)
-            L.check(lib.vt_groupnorm_nhwc(y1.data_ptr(), gamma.data_ptr(), beta.data_ptr(), B, HW, cout, 32, 1e-5, 1, ws.data_ptr(), y.data_ptr(), L.stream_ptr()))
+            y1 = fwd.stem(mod.handles(x.device), x, int(w.shape[0]))
+            y, ws = fwd.groupnorm_relu(y1, gamma, beta)
         ctx.save_for_backward(x, y1, y, ws, gamma)
         return y
 
@@ -1188,8 +1137,8 @@ class _StemTrainFn(torch.autograd.Function):
 
 def stem_train(x, module):
     """``F.relu(bn1(conv1(x)))`` (model/HGFilters.py:167) that a torch graph can contain.  ``x``: (B,Cin,H,W) device tensor; ``module``: an
-    ``encoder.TrainableStem`` (its leaves ``tensors()`` in STEM_PARAMS order and the packed forward handle ``handle(device)``).  Forward: exactly the launches of
-    ``HGFilterEncoder._stem`` + ``_gn(..., relu=True)``; backward: vt_gn_relu_backward_y (mask from the saved output), vt_bias_grad and vt_stem7x7_wgrad.  The image
+    ``encoder.TrainableStem`` (its leaves ``tensors()`` in STEM_PARAMS order and the packed forward handle ``handles(device)``).  Forward: exactly the launches of
+    the inference encoder (``encoder_fwd.stem`` + ``groupnorm_relu``); backward: vt_gn_relu_backward_y (mask from the saved output), vt_bias_grad and vt_stem7x7_wgrad.  The image
     receives no gradient."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
         raise L.VtError("stem_train: x must be a (B,C,H,W) device tensor; there is no CPU path")
@@ -1204,38 +1153,16 @@ def stem_train(x, module):
 class _StackTailTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mod, last, ll, previous, *tensors):
-        # the four launches of the 1 x 1 tail in HGFilterEncoder.__call__ (encoder.py), keeping what the backward reads: ll, raw, out and bn_end's {mean, rstd} area
-        lib = L.lib()
+        # the 1 x 1 tail of encoder_fwd (four launches, two on the last stack), keeping what the backward reads: ll, raw, out and bn_end's {mean, rstd} area
         p = dict(zip(STACK_TAIL_PARAMS, tensors))
-        B, C, H, W = ll.shape
-        Co = int(p["l.weight"].shape[0])
-        dev = ll.device
-
-        def conv(h, x, cin, cout, gn, res, want_stats):
-            o = torch.empty(B, cout, H, W, device=dev, memory_format=torch.channels_last)
-            wo = torch.empty(B * 32 + tiles * B * cout * 2, dtype=torch.float64, device=dev) if want_stats else None
-            L.check(lib.vt_conv1x1_forward(h, x.data_ptr(), cin, 0, gn.data_ptr() if gn is not None else None,
-                                           p["bn_end.weight"].data_ptr() if gn is not None else None, p["bn_end.bias"].data_ptr() if gn is not None else None, 32,
-                                           B, H, W, o.data_ptr(), cout, 0, res.data_ptr() if res is not None else None, cout, 0,
-                                           wo.data_ptr() if want_stats else None, 32, L.stream_ptr()))
-            if want_stats:
-                L.check(lib.vt_groupnorm_finalize(wo.data_ptr(), tiles, B, H * W, cout, 32, 1e-5, L.stream_ptr()))
-            return o, wo
-
-        with torch.cuda.device(dev):
-            tiles = lib.vt_conv3x3_tiles(H, W)
-            h_cl, h_l, h_bl, h_al = mod.handles(dev)
-            raw, ws = conv(h_cl, ll, C, C, None, None, True)
-            out, _ = conv(h_l, raw, C, Co, ws, None, False)
-            ctx.set_materialize_grads(False)
-            ctx.present = [t is not None for t in tensors]
-            ctx.last = bool(last)
-            if last:
-                ctx.save_for_backward(ll, raw, out, ws, *[t for t in tensors if t is not None])
-                return out
-            tmp, _ = conv(h_bl, raw, C, C, ws, previous, False)
-            prev2, ws2 = conv(h_al, out, Co, C, None, tmp, True)
+        with torch.cuda.device(ll.device):
+            raw, ws, out, prev2, ws2 = fwd.stack_tail(mod.handles(ll.device), p["bn_end.weight"], p["bn_end.bias"], ll, previous, int(p["l.weight"].shape[0]), last)
+        ctx.set_materialize_grads(False)
+        ctx.present = [t is not None for t in tensors]
+        ctx.last = bool(last)
         ctx.save_for_backward(ll, raw, out, ws, *[t for t in tensors if t is not None])
+        if last:
+            return out
         ctx.mark_non_differentiable(ws2)
         return out, prev2, ws2
 
@@ -1262,7 +1189,7 @@ class _StackTailTrainFn(torch.autograd.Function):
 def stack_tail_train(ll, previous, module, last):
     """The tail of one stack (model/HGFilters.py:191-201) that a torch graph can contain: ``ll`` (B,C,H,W) the output of top_m, ``previous`` the stack's input
     (ignored when ``last``), ``module`` an ``encoder.TrainableStackTail``.  -> ``out`` when ``last``, else ``(out, previous')`` with the GroupNorm statistics of
-    previous' attached for the next stack's first block.  Forward: exactly the four (two) launches of the tail in ``HGFilterEncoder.__call__``; backward: one
+    previous' attached for the next stack's first block.  Forward: exactly the four (two) launches of the inference tail (``encoder_fwd.stack_tail``); backward: one
     ``vt_stack_tail_backward`` call, an absent upstream gradient passed as NULL."""
     if not (torch.is_tensor(ll) and ll.is_cuda and ll.dim() == 4):
         raise L.VtError("stack_tail_train: ll must be a (B,C,H,W) device tensor; there is no CPU path")
@@ -1279,8 +1206,7 @@ def stack_tail_train(ll, previous, module, last):
     if tuple(pc.shape) != (B, C, H, W):
         raise L.VtError(f"stack_tail_train: previous {tuple(pc.shape)} does not fit ll {tuple(llc.shape)}")
     out, prev2, ws2 = _StackTailTrainFn.apply(module, False, llc, pc, *tensors)
-    prev2._vt_stats = [ws2, int(L.lib().vt_conv3x3_tiles(H, W)), True]
-    return out, prev2
+    return out, fwd.attach_stats(prev2, ws2, int(L.lib().vt_conv3x3_tiles(H, W)), finalized=True)
 
 
 # --------------------------------------------------------------------------------------------------
