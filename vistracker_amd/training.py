@@ -4,10 +4,14 @@
 ``validate`` is one batch of the reference's ``compute_val_loss`` (trainer/trainer.py:321-346: query, then ``get_errors``, no gradient) with no host labelling.
 
 Out of scope here: file and ``KinectTransform`` IO (the meshes arrive in camera-local coordinates), image loading (``SequenceLoader(device_prep=True)``
-builds the network inputs), ``smpl_vect`` (``load_neighbour_h``), the feature-map and encoder gradients, learning-rate schedules, checkpoint directories.
+builds the network inputs), ``smpl_vect`` (``load_neighbour_h``), data loaders over the sampled files, checkpoint directories.
 
 ``DecoderTrainer`` is the reference's ``Trainer.train_step`` (trainer/trainer.py:97-106) for the decoder parameter group: the five point decoders of a checkpoint
 are fine-tuned on labelled batches with the encoder, and so the feature maps, frozen.
+
+``SIFNetTrainer`` is the same ``train_step`` for the whole network (model/chore_triplane.py:60-164, model/chore_tri_vis.py): the image encoder and the shared
+triplane encoder (``encoder.TrainableHGFilter``) and the five decoders (``ops.DecoderParams``) step together from one ``error.backward()``, with the reference's
+``MultiStepLR`` as the host function ``multistep_lr``.  It adds no kernel: it is the host layer that joins the merged blocks.
 """
 from __future__ import annotations
 
@@ -131,4 +135,140 @@ class DecoderTrainer:
         out = SIFNetQuery(self.params.to_decoders(), camera=self.net.camera, device=self.net.device)
         out.maps, out.encoder = self.net.maps, self.net.encoder
         out.loss_weights, out.vis_loss_name = list(self.net.loss_weights), self.net.vis_loss_name
+        return out
+
+
+def multistep_lr(lr0, milestones, gamma, epoch):
+    """``torch.optim.lr_scheduler.MultiStepLR(milestones, gamma)`` as a function of the epoch counter: lr0 . gamma^(number of milestones <= epoch), multiplied up
+    milestone by milestone as the scheduler does, so the value is the scheduler's to the last bit (a milestone listed k times counts k times)."""
+    lr = float(lr0)
+    for m in sorted(set(milestones)):
+        if m <= epoch:
+            lr *= float(gamma) ** list(milestones).count(m)
+    return lr
+
+
+IMAGE_PREFIX, TRIPLANE_PREFIX = "image_filter.", "triplane_encoder."
+
+
+def network_state_dict(image, tri, params):
+    """the whole network under the reference's checkpoint keys: ``image_filter.*`` and ``triplane_encoder.*`` from the two ``TrainableHGFilter``s, ``df.0.weight``
+    ... from the ``ops.DecoderParams``; copies"""
+    out = {IMAGE_PREFIX + k: v for k, v in image.state_dict().items()}
+    out.update({TRIPLANE_PREFIX + k: v for k, v in tri.state_dict().items()})
+    out.update(params.state_dict())
+    return out
+
+
+def _strip_module(sd):
+    return {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+
+
+class SIFNetTrainer:
+    """``Trainer.train_step`` (trainer/trainer.py:97-106) for the whole ``CHORETriplaneVisibility``: the image encoder (``.image``, Cin 5) and the shared triplane
+    encoder (``.tri``, Cin 1, applied once to the 3B single-channel renders as ``SIFNetEncoder._chunk_eager`` batches them) are ``TrainableHGFilter``s, the five
+    decoders an ``ops.DecoderParams`` (``.params``).  One ``EncoderAdam`` per encoder and one ``ops.FusedAdam`` over the decoders' flat buffer step at the same
+    learning rate; they are built here, before any forward (``EncoderAdam`` re-homes every leaf's ``.data``).
+
+        tr = SIFNetTrainer(torch.load(ckpt)["model_state_dict"], camera)
+        for epoch in range(epochs):
+            tr.set_step(epoch)                      # MultiStepLR(milestones, gamma); advancing the epoch is the caller's
+            for batch, images, cc in loader:
+                error, losses_all = tr.train_step(batch, images, cc)
+        net = tr.export(images)                     # a SIFNetQuery with the trained decoders and a SIFNetEncoder of the trained encoders, maps of `images` set
+
+    ``sd`` carries the reference's keys (a leading ``module.`` is stripped).  Only the shared triplane encoder is served: per-view encoders
+    (``triplane_encoder_0.`` ...) raise.  The query needs as many triplane stacks as image stacks (chore_triplane.py:146-147 indexes both with one counter)."""
+
+    def __init__(self, sd, camera=None, num_stack=3, num_hourglass=2, triplane_stack=3, lr=1e-3, milestones=(), gamma=0.3, max_dist=5.0,
+                 loss_weights=ops.LOSS_WEIGHTS, device="cuda:0"):
+        sd = _strip_module(sd)
+        if any(k.startswith("triplane_encoder_") for k in sd):
+            raise L.VtError("SIFNetTrainer: this checkpoint holds per-view triplane encoders (triplane_encoder_0. ...); only the shared form "
+                            "(triplane_encoder.) is trained here")
+        if int(num_stack) != int(triplane_stack):
+            raise L.VtError(f"SIFNetTrainer: {num_stack} image stacks and {triplane_stack} triplane stacks; the training query pairs them one to one")
+        from .encoder import EncoderAdam, TrainableHGFilter
+        from .sifnet import SIFNetQuery
+        self.device, self.max_dist = device, float(max_dist)
+        self.num_stack, self.num_hourglass = int(num_stack), int(num_hourglass)
+        self.lr0, self.milestones, self.gamma, self.epoch = float(lr), tuple(milestones), float(gamma), 0
+        self.image = TrainableHGFilter.from_state_dict(sd, IMAGE_PREFIX, num_stack=num_stack, num_hourglass=num_hourglass, device=device)
+        self.tri = TrainableHGFilter.from_state_dict(sd, TRIPLANE_PREFIX, num_stack=triplane_stack, num_hourglass=num_hourglass, device=device)
+        self.net = SIFNetQuery(SIFNetQuery.decoders_from_state_dict(sd), camera=camera, device=device)          # serves query_train and get_errors
+        self.net.loss_weights = list(loss_weights)
+        self.camera = self.net.camera
+        self.params = ops.DecoderParams.from_decoders(self.net.decoders, cam=self.camera.as_cam5(), device=device)
+        self.image_optimizer, self.tri_optimizer = EncoderAdam(self.image, lr=lr), EncoderAdam(self.tri, lr=lr)
+        self.optimizer = ops.FusedAdam([self.params.flat], lr=lr)
+        self.set_step(0)
+
+    @property
+    def lr(self):
+        """the learning rate of the next step"""
+        return self.image_optimizer.lr
+
+    def set_step(self, k):
+        """the epoch counter of the reference's ``MultiStepLR``: the three optimisers step at ``multistep_lr(lr0, milestones, gamma, k)`` from now on"""
+        self.epoch = int(k)
+        lr = multistep_lr(self.lr0, self.milestones, self.gamma, self.epoch)
+        self.image_optimizer.lr = self.tri_optimizer.lr = lr
+        self.optimizer.lrs = [lr] * len(self.optimizer.params)
+        return lr
+
+    def forward(self, images):
+        """``CHORETriplane.filter`` in train mode on (B,8,H,W) inputs -> a list of S ``ops.FeatureMaps``, one per stack.  The NHWC tensors are permuted views of the
+        encoders' channels-last outputs (no copy) and carry autograd; the three views of the triplane encoder are batch slices of one output; the stacks share
+        ``tmpx`` / ``tri_tmpx{v}``, detached as the reference detaches them (HGFilters.py:203)."""
+        assert images.dim() == 4 and images.shape[1] == 8, f"given image shape invalid: {tuple(images.shape)}"
+        x = images.to(self.device).float()
+        B = x.shape[0]
+        feats, tmpx, _ = self.image(x[:, :5])
+        tfeats, ttmpx, _ = self.tri(x[:, 5:8].transpose(0, 1).reshape(3 * B, 1, *x.shape[2:]))
+        shared = {"tmpx": tmpx.permute(0, 2, 3, 1)}
+        for v in range(3):
+            shared[f"tri_tmpx{v}"] = ttmpx[v * B:(v + 1) * B].permute(0, 2, 3, 1)
+        maps = []
+        for s in range(self.num_stack):
+            d = dict(shared)
+            d["im_feat"] = feats[s].permute(0, 2, 3, 1)
+            for v in range(3):
+                d[f"tri_feat{v}"] = tfeats[s][v * B:(v + 1) * B].permute(0, 2, 3, 1)
+            maps.append(ops.FeatureMaps(d))
+        return maps
+
+    def train_step(self, batch, images, crop_center):
+        """one step on a batch of ``make_training_batch`` and its (B,8,H,W) network input: zero_grad, both encoder forwards, the S per-stack ``FeatureMaps``,
+        ``query_train`` over all stacks, ``get_errors``, one ``error.backward()`` (decoders, then both encoders, through the maps), the three optimiser steps.
+        -> (error (), losses_all (6,)): float64 device tensors of the objective BEFORE the update; nothing here waits on the host."""
+        self.image_optimizer.zero_grad(); self.tri_optimizer.zero_grad(); self.optimizer.zero_grad()
+        maps = self.forward(images)
+        self.net.query_train(self.params, batch["points"], crop_center=crop_center, body_center=batch["body_center"], maps=maps)
+        error, losses_all = self.net.get_errors(batch["df_h"], batch["df_o"], batch["labels"], batch["pca_axis"], self.max_dist, batch["body_center"],
+                                                batch["obj_center"], visibility=batch["visibility"])
+        error.backward()
+        self.image_optimizer.step(); self.tri_optimizer.step(); self.optimizer.step()
+        return error.detach(), losses_all
+
+    def state_dict(self):
+        """the whole network under the reference's checkpoint keys (``image_filter.*``, ``triplane_encoder.*``, ``df.0.weight`` ...); device copies.  It loads
+        back into a new ``SIFNetTrainer``."""
+        return network_state_dict(self.image, self.tri, self.params)
+
+    def export(self, images=None):
+        """-> a new ``SIFNetQuery`` holding the trained decoders (packed by ``vt_sifnet_create`` as any checkpoint's) and, as ``.encoder``, a ``SIFNetEncoder`` built
+        from the trained encoder weights, with this trainer's camera and loss settings.  ``images`` (B,8,H,W), when given, are encoded with the trained weights and set as its maps, so that it goes straight into
+        ``validate``; without them the maps are None (the generator and the fit loops call ``filter`` themselves; the trainer keeps no input of a step alive).
+        Host traffic: the decoders are read back once here, as ``DecoderTrainer.export`` does.  The encoder weights are handed over as device tensors, but a
+        ``SIFNetEncoder`` packs its convolutions on the host at their first use (``HGFilterEncoder._handle``: one read back per convolution, about 2 x 94 in the
+        shipped configuration), which happens here when ``images`` are given and at the first ``filter`` otherwise."""
+        from .encoder import SIFNetEncoder
+        from .sifnet import SIFNetQuery
+        out = SIFNetQuery(self.params.to_decoders(), camera=self.camera, device=self.device)
+        enc_sd = {k: v for k, v in self.state_dict().items() if k.startswith((IMAGE_PREFIX, TRIPLANE_PREFIX))}
+        out.encoder = SIFNetEncoder(enc_sd, num_stack=self.num_stack, num_hourglass=self.num_hourglass, triplane_stack=self.num_stack, shared_encoder=True,
+                                    device=self.device)
+        out.loss_weights, out.vis_loss_name = list(self.net.loss_weights), self.net.vis_loss_name
+        if images is not None:
+            out.filter(images)
         return out
