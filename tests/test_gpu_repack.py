@@ -475,6 +475,76 @@ def test_replaced_leaf_is_followed_and_reported(monkeypatch):
         opt.step()
 
 
+# ---- the inference encoder on the same store --------------------------------------------------------------------------------------------------------------------
+CREATE_DEVICE = ("vt_conv3x3_create_device", "vt_conv1x1_create_device", "vt_stem7x7_create_device")
+
+
+def make_inference(tag, host_repack, monkeypatch):
+    """a fresh HGFilterEncoder of a whole-filter case with strict routes, and its input"""
+    from vistracker_amd import encoder as E
+    monkeypatch.setattr(E._PackedHandles, "host_repack", host_repack)
+    cin, tmpx, hg, seed = EM.FILTER_CASES[tag]
+    P = EM.filter_make_params(cin, tmpx, hg, EM.FILTER_NUM_STACK, EM.FILTER_DEPTH, seed)
+    enc = E.HGFilterEncoder(P, "", EM.FILTER_NUM_STACK, EM.FILTER_DEPTH, device=DEV)
+    enc.strict_routes = True
+    return enc, cl(np.random.RandomState(seed + 1).rand(EM.FILTER_B, cin, EM.FILTER_H, EM.FILTER_W)), P
+
+
+def all_outputs(enc, x):
+    outputs, tmpx, normx = enc(x)
+    return [bits(t).clone() for t in outputs + [tmpx, normx]]
+
+
+@pytest.mark.parametrize("tag", list(EM.FILTER_CASES))
+def test_inference_device_packing_is_host_packing_bit_for_bit(tag, monkeypatch):
+    """the stem's 7 x 7 and the 3 x 3 weights are stored channels-last: both packings must read them in NCHW order"""
+    got = {}
+    for host in (True, False):
+        enc, x, _ = make_inference(tag, host, monkeypatch)
+        assert not enc.sd["conv1.weight"].is_contiguous() or enc.sd["conv1.weight"].shape[1] == 1
+        assert not enc.sd["conv3.conv1.weight"].is_contiguous()
+        got[host] = all_outputs(enc, x)
+        assert enc.routes and not any(k.startswith("miopen:") for k in enc.routes), dict(enc.routes)
+        assert all(ent.on_host == host for ent in enc._handles.values()) and len(enc._handles) == sum(enc.routes.values())
+    assert len(got[True]) == EM.FILTER_NUM_STACK + 2 == len(got[False])
+    assert all(torch.equal(a, b) for a, b in zip(got[True], got[False])), [i for i, (a, b) in enumerate(zip(got[True], got[False])) if not torch.equal(a, b)]
+    assert all(bool(a.view(torch.float32).abs().sum() > 0) and bool(torch.isfinite(a.view(torch.float32)).all()) for a in got[False])
+
+
+def test_inference_needs_no_host(monkeypatch):
+    """with every way to the host barred, the first forward of a fresh HGFilterEncoder completes: one vt_*_create_device per distinct convolution; the second
+    forward packs nothing and gives the same bits"""
+    from vistracker_amd import _lib
+    enc, x, P = make_inference("image", False, monkeypatch)
+    calls = []
+
+    def counted(name):
+        real = getattr(_lib.lib(), name)
+
+        def f(*a):
+            calls.append(name)
+            return real(*a)
+        return f
+
+    def barred(*a, **k):
+        raise AssertionError("the inference encoder went to the host")
+
+    with monkeypatch.context() as mp:
+        for name in CREATE_DEVICE:
+            mp.setattr(_lib.lib(), name, counted(name))
+        mp.setattr(torch.Tensor, "cpu", barred)
+        mp.setattr(torch.Tensor, "numpy", barred)
+        mp.setattr(torch.cuda, "synchronize", barred)
+        first = all_outputs(enc, x)
+        n_first = len(calls)
+        second = all_outputs(enc, x)
+    convs = [k for k, v in P.items() if np.ndim(v) == 4]            # every convolution weight of the filter is used once per forward
+    assert n_first == len(convs) == len(enc._handles) and len(calls) == n_first, (n_first, len(convs), len(calls))
+    assert calls.count("vt_stem7x7_create_device") == 1 and calls.count("vt_conv1x1_create_device") == sum(np.shape(P[k])[2] == 1 for k in convs)
+    assert not any(k.startswith("miopen:") for k in enc.routes)
+    assert all(torch.equal(a, b) for a, b in zip(first, second))
+
+
 def test_version_change_repacks_in_place(monkeypatch):
     """without EncoderAdam: an in-place update that the version counter sees is followed by vt_*_repack on the same handle"""
     from vistracker_amd import encoder as E

@@ -164,6 +164,34 @@ def test_round_trips(env):
                for name, mod in SM.MODULES.items() for i, (w, b) in zip((0, 2, 4, 6), net.decoders[name]) for kind, k in (("weight", f"{mod}.{i}.weight"), ("bias", f"{mod}.{i}.bias")))
 
 
+def test_export_packs_nothing_on_the_host(env, monkeypatch):
+    """export(images) encodes with handles packed on the device; its eight maps are those of a SIFNetEncoder built from state_dict() that packs on the host"""
+    from vistracker_amd import _lib, encoder as E, ops
+    tr = make(env)
+    tr.train_step(env["batch"], env["images"], env["cc"])
+    calls = []
+
+    def counted(name):
+        real = getattr(_lib.lib(), name)
+
+        def f(*a):
+            calls.append(name)
+            return real(*a)
+        return f
+
+    with monkeypatch.context() as mp:
+        for name in ("vt_conv3x3_create", "vt_conv1x1_create", "vt_stem7x7_create"):
+            mp.setattr(_lib.lib(), name, counted(name))
+        net = tr.export(env["images"])
+        assert calls == [] and net.encoder.image._handles and not any(ent.on_host for e in (net.encoder.image, net.encoder.tri[0]) for ent in e._handles.values())
+        mp.setattr(E._PackedHandles, "host_repack", True)
+        ref = E.SIFNetEncoder(tr.state_dict(), num_stack=SM.NUM_STACK, num_hourglass=SM.DEPTH, triplane_stack=SM.NUM_STACK, device=DEV)
+        want = ref(env["images"])
+        assert len(calls) == len(ref.image._handles) + len(ref.tri[0]._handles) > 0           # the reference did pack on the host
+    assert len(want.t) == len(net.maps.t) == len(ops.MAP_ORDER) == 8
+    assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(net.maps.t, want.t)), [k for k, a, b in zip(ops.MAP_ORDER, net.maps.t, want.t) if not torch.equal(a, b)]
+
+
 # ---- 6: the schedule ---------------------------------------------------------------------------------------------------------------------------------------------------
 def test_schedule_is_the_learning_rate_set_directly(env):
     lr0 = 1e-3

@@ -144,6 +144,40 @@ def test_model_matches_the_recorded_reference(tag):
         assert err <= 4 * e32[n] + 1e-30, (n, err, e32[n])
 
 
+def test_state_dict_reader_strips_module_and_prefix():
+    """encoder.state_dict_under / as_f32 behind the three from_state_dict: a 'module.'-prefixed state dict and a plain one give the same state_dict(), under a
+    prefix and without one; a missing key raises the KeyError it always raised"""
+    from vistracker_amd import encoder as E
+    assert E.state_dict_under({"module.p.a": 1, "p.b": 2, "q.p.c": 3, "module.q.d": 4}, "p.") == {"a": 1, "b": 2}
+    assert E.state_dict_under({"module.a": 1, "b": 2}, "") == {"a": 1, "b": 2}
+    t = E.as_f32(np.arange(6, dtype=np.float64).reshape(2, 3), "cpu")
+    assert t.dtype == torch.float32 and t.device.type == "cpu" and not t.requires_grad and E.as_f32(t, "cpu").data_ptr() == t.data_ptr()
+    P = EM.filter_make_params(1, 32, 64, 2, 1, 31)
+    block = lambda sd, p: E.TrainableConvBlock.from_state_dict(sd, p, device="cpu")            # noqa: E731
+    makers = {"conv3.": block, "conv4.": block,         # an identity block and one with a projection
+              "m0.": lambda sd, p: E.TrainableHourglass.from_state_dict(sd, p, depth=1, device="cpu"),
+              "": lambda sd, p: E.TrainableHGFilter.from_state_dict(sd, p, num_stack=2, num_hourglass=1, device="cpu")}
+    for sub, make in makers.items():
+        for outer in ("", "image_filter."):
+            plain = {outer + k: v for k, v in P.items()}
+            a, b = make(plain, outer + sub).state_dict(), make({"module." + k: v for k, v in plain.items()}, outer + sub).state_dict()
+            assert list(a) == list(b) and len(a) >= sum(k.startswith(sub) for k in P) > 0
+            assert all(a[k].dtype == torch.float32 and torch.equal(a[k], b[k]) and np.array_equal(a[k].numpy(), P[sub + k]) for k in a if sub + k in P)
+    for sub, make, key, text in (("conv3.", makers["conv3."], "conv3.bn2.bias", "no ConvBlock parameter 'conv3.bn2.bias'"),
+                                 ("m0.", makers["m0."], "m0.b2_plus_1.conv1.weight", "no ConvBlock parameter 'm0.b2_plus_1.conv1.weight'"),
+                                 ("", makers[""], "bn_end1.weight", "no encoder parameter 'bn_end1.weight'"),
+                                 ("", makers[""], "top_m_0.conv3.weight", "no ConvBlock parameter 'top_m_0.conv3.weight'")):
+        with pytest.raises(KeyError) as e:
+            make({"module." + k: v for k, v in P.items() if k != key}, sub)
+        assert e.value.args[0] == text
+    with pytest.raises(KeyError) as e:
+        E.HGFilterEncoder({"module.image_filter." + k: v for k, v in P.items()}, "triplane_encoder.", 2, 1, device="cpu")
+    assert e.value.args[0] == "no encoder weights under prefix 'triplane_encoder.'"
+    with pytest.raises(KeyError) as e:
+        E.TrainableConvBlock.from_state_dict({k: v for k, v in P.items() if not k.startswith(("conv4.downsample.0", "conv4.bn4"))}, "conv4.", device="cpu")
+    assert e.value.args[0] == "'conv4.downsample.2.weight' without the projection's norm"
+
+
 def test_stats_hand_over_finalizes_once(monkeypatch):
     """encoder_fwd.attach_stats / stats_of with the library call stubbed: nothing attached -> None; partial sums are finalized at their first use, with the
     tensor's own sizes, and never again; an entry attached as finalized is handed over as it is"""

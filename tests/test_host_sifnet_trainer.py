@@ -43,14 +43,14 @@ def shipped_state_dict(names):
 
 def test_state_dict_keys_are_the_references():
     from vistracker_amd import ops, training
-    from vistracker_amd.encoder import TrainableHGFilter
+    from vistracker_amd.encoder import TrainableHGFilter, state_dict_under
     from vistracker_amd.sifnet import SIFNetQuery
     with open(os.path.join(GOLDEN, "sifnet_state_dict_keys.txt")) as f:
         names = f.read().split()
     assert len(names) == len(set(names)) and any(k.startswith("image_filter.") for k in names) and any(k.startswith("triplane_encoder.") for k in names)
     sd = {"module." + k: v for k, v in shipped_state_dict(names).items()}
     assert {k[7:] for k in sd} == set(names)
-    own = training._strip_module(sd)
+    own = state_dict_under(sd, "")
     image = TrainableHGFilter.from_state_dict(own, training.IMAGE_PREFIX, num_stack=3, num_hourglass=2, device="cpu")
     tri = TrainableHGFilter.from_state_dict(own, training.TRIPLANE_PREFIX, num_stack=3, num_hourglass=2, device="cpu")
     params = ops.DecoderParams.from_decoders(SIFNetQuery.decoders_from_state_dict(own), device="cpu")

@@ -6,6 +6,8 @@ convolution library (MIOpen through ``torch.nn.functional``); since round 6 ever
 kernels (csrc/conv.hip: 3 x 3 and 1 x 1 as split-f16 implicit GEMMs; csrc/stem.hip: the 7 x 7 stem in fp32) and ``torch.nn.functional`` is only the
 counted fallback for layer shapes those kernels do not serve (``routes``, ``strict_routes``) and the host path of the CPU tests.  Everything is in
 channels-last memory format so that the outputs ARE the NHWC feature maps the fused query kernel gathers from -- no NCHW->NHWC pass.
+The kernels read their weights from packed handles; ``_PackedHandles`` is the one store of them, for this encoder and for the ``Trainable*`` modules that issue
+the same launches (``encoder_fwd``): packed on the device from the weight tensor at a convolution's first use, repacked in place when the tensor changes.
 Weights are addressed by the reference's ``state_dict`` names, so a VisTracker checkpoint loads unchanged:
 
     enc = SIFNetEncoder.from_state_dict(torch.load(ckpt)["model_state_dict"])
@@ -32,6 +34,21 @@ from . import _lib as L
 from . import encoder_fwd as fwd
 from . import ops
 from .encoder_fwd import stats_of as _stats_of          # noqa: F401 -- the name the tests know
+
+
+def state_dict_under(sd, prefix):
+    """the entries of a state dict whose key, a leading 'module.' stripped, starts with ``prefix`` -> {key without the prefix: value}"""
+    keys = ((k[7:] if k.startswith("module.") else k, v) for k, v in sd.items())
+    return {k[len(prefix):]: v for k, v in keys if k.startswith(prefix)}
+
+
+def as_f32(v, device):
+    """a state dict's value (tensor or array) as an fp32 tensor on ``device``; no copy of one that is that already"""
+    return torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).detach().to(device=device, dtype=torch.float32)
+
+
+def _leaf(v, device):
+    return as_f32(v, device).contiguous().clone().requires_grad_(True)
 
 
 def avgpool2x2(x):
@@ -67,7 +84,86 @@ REPACK_CONV3X3, REPACK_CONV1X1, REPACK_STEM7X7 = 0, 1, 2          # include/vist
 _HANDLE_FN = {REPACK_CONV3X3: "vt_conv3x3", REPACK_CONV1X1: "vt_conv1x1", REPACK_STEM7X7: "vt_stem7x7"}
 
 
-class HGFilterEncoder:
+@dataclasses.dataclass(eq=False, slots=True)
+class _Packed:
+    """one packed forward handle and the tensor pair (training leaves, or an inference encoder's stored weights) it was packed from"""
+    handle: object          # ctypes.c_void_p
+    version: object         # (weight version, bias version) when it was packed; None = repack at the next use
+    kind: int               # REPACK_*
+    weight: torch.Tensor
+    bias: object            # leaf or None
+    on_host: bool           # packed on the host (vt_*_create): replaced, not repacked in place
+
+
+class _PackedHandles:
+    """The packed forward handles of a module's convolutions, one per (weight, bias) tensor pair: the one store of the package, for the inference encoder
+    (``HGFilterEncoder``, pairs out of its state dict) and the ``Trainable*`` modules (leaf pairs) alike, and the one owner of the handles' lifetime.  A handle is
+    created ONCE, at the convolution's first use, on the device and straight from the tensor (``vt_*_create_device``), and repacked in place (``vt_*_repack``, two
+    launches on the current stream) when a version counter of its pair changed since it was packed: no copy to the host, no synchronisation, no destroy -- the
+    handle's address is stable for the life of the module, and ordering on the stream protects the launches that still read the old packing.  ``EncoderAdam``
+    repacks all handles of a network in one plan and marks them current, so that the check here finds nothing to do.  An update that goes round the version
+    counters (a kernel writing through ``data_ptr()``, as ``ops.FusedAdam`` does) has to say so with ``invalidate_handles()``.
+
+    ``VT_ENCODER_HOST_REPACK=1`` (``host_repack``) keeps the path this replaced, as the reference of the bit-equality tests and for A/B: synchronise, destroy the
+    handle, pull the tensor to the host, pack it there with ``vt_*_create`` and copy it back up, per convolution and change.  It is the package's only use of the
+    host packers."""
+    host_repack = os.environ.get("VT_ENCODER_HOST_REPACK", "0") != "0"
+
+    def _init_handles(self):
+        self._handles = {}          # key -> _Packed
+
+    def _packed(self, key, kind, w, b, device):
+        import ctypes as C
+        ent = self._handles.get(key)
+        ver = (w._version, b._version if b is not None else -1)
+        if ent is not None and ent.version == ver and ent.weight is w and ent.bias is b:
+            return ent.handle
+        lib, fn = L.lib(), _HANDLE_FN[kind]
+        cout, cin = w.shape[:2]
+        bias_arg = kind != REPACK_CONV3X3
+        wc = w.detach().contiguous()            # the packers read (Cout, Cin, ky * k + kx) in NCHW order: a copy only of a weight stored channels-last
+        if ent is not None and (self.host_repack or ent.on_host):
+            torch.cuda.synchronize(device)          # launches that read the old packing may still be queued
+            getattr(lib, fn + "_destroy")(ent.handle)
+            ent = None
+        with torch.cuda.device(device):
+            if self.host_repack:
+                wh = np.ascontiguousarray(wc.cpu().numpy().reshape(cout, cin, -1), np.float32)
+                bh = np.ascontiguousarray(b.detach().cpu().numpy(), np.float32) if b is not None else None
+                h = C.c_void_p()
+                args = (wh.ctypes.data, bh.ctypes.data if bh is not None else None) if bias_arg else (wh.ctypes.data,)
+                L.check(getattr(lib, fn + "_create")(C.byref(h), *args, cout, cin, L.stream_ptr()))
+                ent = _Packed(h, ver, kind, w, b, True)
+            else:
+                args = (L.dptr(wc), L.dptr(b.detach()) if b is not None else None) if bias_arg else (L.dptr(wc),)
+                if ent is None:
+                    h = C.c_void_p()
+                    L.check(getattr(lib, fn + "_create_device")(C.byref(h), *args, cout, cin, L.stream_ptr()))
+                    ent = _Packed(h, ver, kind, w, b, False)
+                else:
+                    L.check(getattr(lib, fn + "_repack")(ent.handle, *args, L.stream_ptr()))
+                    ent.version, ent.weight, ent.bias = ver, w, b          # a replaced leaf object is the pair the handle follows from now on
+        self._handles[key] = ent
+        return ent.handle
+
+    def invalidate_handles(self):
+        """the leaves were written behind the version counters: repack every handle at its next use"""
+        for ent in self._handles.values():
+            ent.version = None
+
+    def _mark_handles_current(self):
+        for ent in self._handles.values():
+            ent.version = (ent.weight._version, ent.bias._version if ent.bias is not None else -1)
+
+    def __del__(self):
+        try:
+            for ent in getattr(self, "_handles", {}).values():
+                getattr(L.lib(), _HANDLE_FN[ent.kind] + "_destroy")(ent.handle)
+        except Exception:
+            pass
+
+
+class HGFilterEncoder(_PackedHandles):
     # 3x3 convolutions with 32 / 64 / 128 output channels and Cin % 32 == 0 and the 1x1 convolutions (conv_last / l / bl / al of a stack, the
     # ConvBlocks' projections) run on the split-f16 implicit-GEMM kernel (csrc/conv.hip, vt_conv3x3_* / vt_conv1x1_*); the 7x7 stem (Cout 32 / 64, Cin <= 8) on
     # the fp32 kernel of csrc/stem.hip (round 6: until then the encoder's one MIOpen call).  Other shapes fall back to MIOpen -- counted, and refused
@@ -95,42 +191,15 @@ class HGFilterEncoder:
         self.device = torch.device(device)
         self.num_stack, self.depth = num_stack, num_hourglass
         self.sd = {}
-        for k, v in sd.items():
-            k = k[7:] if k.startswith("module.") else k
-            if k.startswith(prefix):
-                t = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).detach().float().to(self.device)
-                self.sd[k[len(prefix):]] = t.contiguous(memory_format=torch.channels_last) if t.dim() == 4 else t
+        for k, v in state_dict_under(sd, prefix).items():
+            t = as_f32(v, self.device)
+            self.sd[k] = t.contiguous(memory_format=torch.channels_last) if t.dim() == 4 else t
         if "conv1.weight" not in self.sd:
             raise KeyError(f"no encoder weights under prefix '{prefix}'")
         self.in_channels = self.sd["conv1.weight"].shape[1]
-        self._conv_handles = {}
+        self._init_handles()
         import collections
         self.routes = collections.Counter()
-
-    def __del__(self):
-        try:
-            for (kind, _), h in getattr(self, "_conv_handles", {}).items():
-                getattr(L.lib(), _HANDLE_FN[kind] + "_destroy")(h)
-        except Exception:
-            pass
-
-    def _handle(self, kind, wname, bname=None):
-        """the packed forward handle of one convolution, created at its first use: packed on the host (``vt_*_create``) from the NCHW-contiguous copy of the
-        weight (the stored one is channels-last) as (Cout, Cin, ky * k + kx), with the bias ``bname`` if the state dict has it (1 x 1 and stem only)"""
-        import ctypes as C
-        h = self._conv_handles.get((kind, wname))
-        if h is None:
-            w = self.sd[wname]; cout, cin = w.shape[:2]
-            wh = np.ascontiguousarray(w.contiguous().cpu().numpy().reshape(cout, cin, -1), np.float32)
-            args = [wh.ctypes.data]
-            if kind != REPACK_CONV3X3:
-                bh = np.ascontiguousarray(self.sd[bname].cpu().numpy(), np.float32) if bname in self.sd else None
-                args.append(bh.ctypes.data if bh is not None else None)
-            h = C.c_void_p()
-            with torch.cuda.device(self.device):
-                L.check(getattr(L.lib(), _HANDLE_FN[kind] + "_create")(C.byref(h), *args, cout, cin, L.stream_ptr()))
-            self._conv_handles[(kind, wname)] = h
-        return h
 
     def _stem(self, x):
         """conv1 (HGFilters.py:118-130, 7 x 7 / stride 2 / pad 3 with bias) -> channels-last (B, 64, ceil(H/2), ceil(W/2))"""
@@ -138,7 +207,8 @@ class HGFilterEncoder:
         if not (x.is_cuda and self.use_hip_conv and self.use_hip_stem and cout in (32, 64) and cin <= 8 and tuple(w.shape[2:]) == (7, 7)):
             return self._miopen("stem7x7", x, w, self.sd.get("conv1.bias"), 2, 3)
         self.routes["hip7x7"] += 1
-        return fwd.stem(self._handle(REPACK_STEM7X7, "conv1.weight", "conv1.bias"), x.contiguous(memory_format=torch.channels_last), cout)
+        h = self._packed((REPACK_STEM7X7, "conv1.weight"), REPACK_STEM7X7, w, self.sd.get("conv1.bias"), self.device)
+        return fwd.stem(h, x.contiguous(memory_format=torch.channels_last), cout)
 
     def _hip_conv1x1_ok(self, wname, H, W, cuda):
         cout, cin = self.sd[wname].shape[:2]
@@ -185,7 +255,7 @@ class HGFilterEncoder:
                     nxt = i < 3 and self._hip_conv_ok(p + f"conv{i + 1}.weight", H, W, True)
                     ws_out = fwd.partials_workspace(B, co, tiles, x.device) if nxt else None
                     self.routes["hip3x3"] += 1
-                    L.check(lib.vt_conv3x3_forward_gn_stats(self._handle(REPACK_CONV3X3, wn), src.data_ptr(), cstride, coff, ws.data_ptr(),
+                    L.check(lib.vt_conv3x3_forward_gn_stats(self._packed((REPACK_CONV3X3, wn), REPACK_CONV3X3, sd[wn], None, self.device), src.data_ptr(), cstride, coff, ws.data_ptr(),
                                                             sd[gn + ".weight"].data_ptr(), sd[gn + ".bias"].data_ptr(), 32, B, H, W, out.data_ptr(), Ct, off,
                                                             ws_out.data_ptr() if nxt else None, 32, L.stream_ptr()))
                     ws_prev = ws_out
@@ -214,13 +284,15 @@ class HGFilterEncoder:
             if self._hip_conv1x1_ok(wp, H, W, True):
                 # the projection's GroupNorm normalises the same tensor as bn1: same {mean, rstd}, its own gamma / beta, fused into the staging
                 self.routes["hip1x1"] += 1
-                res, _ = fwd.conv1x1(self._handle(REPACK_CONV1X1, wp), x, sd[wp].shape[0], gn=(ws, sd[p + "downsample.0.weight"], sd[p + "downsample.0.bias"]))
+                res, _ = fwd.conv1x1(self._packed((REPACK_CONV1X1, wp), REPACK_CONV1X1, sd[wp], None, self.device), x, sd[wp].shape[0],
+                                     gn=(ws, sd[p + "downsample.0.weight"], sd[p + "downsample.0.bias"]))
             else:
                 res = self._miopen(p + "downsample", _gn(x, sd, p + "downsample.0", relu=True), sd[wp]).contiguous(memory_format=torch.channels_last)
         assert res.shape[1] == Ct
         self.routes["hip3x3"] += 3
-        return fwd.conv_block([self._handle(REPACK_CONV3X3, p + f"conv{i}.weight") for i in (1, 2, 3)], [sd[p + f"bn{i}.weight"] for i in (1, 2, 3)],
-                              [sd[p + f"bn{i}.bias"] for i in (1, 2, 3)], x, ws, res, couts, self.producer_stats and Ct % 32 == 0)[0]
+        handles = [self._packed((REPACK_CONV3X3, n), REPACK_CONV3X3, sd[n], None, self.device) for n in (p + "conv1.weight", p + "conv2.weight", p + "conv3.weight")]
+        return fwd.conv_block(handles, [sd[p + f"bn{i}.weight"] for i in (1, 2, 3)], [sd[p + f"bn{i}.bias"] for i in (1, 2, 3)], x, ws, res, couts,
+                              self.producer_stats and Ct % 32 == 0)[0]
 
     def _hourglass(self, level, x, p):
         up1 = self._conv_block(x, f"{p}b1_{level}.")
@@ -250,7 +322,7 @@ class HGFilterEncoder:
             names = [f"conv_last{i}.weight", f"l{i}.weight"] + ([] if last else [f"bl{i}.weight", f"al{i}.weight"])
             if ll.is_cuda and all(self._hip_conv1x1_ok(n, H, W, True) for n in names):
                 # the tail of a stack as four launches of the 1 x 1 kernel (two on the last stack)
-                handles = [self._handle(REPACK_CONV1X1, n, n[:-6] + "bias") for n in names] + [None] * (4 - len(names))
+                handles = [self._packed((REPACK_CONV1X1, n), REPACK_CONV1X1, sd[n], sd.get(n[:-6] + "bias"), self.device) for n in names] + [None] * (4 - len(names))
                 self.routes["hip1x1"] += len(names)
                 ll, previous = (t.contiguous(memory_format=torch.channels_last) for t in (ll, previous))
                 _, _, out, nxt, _ = fwd.stack_tail(handles, sd[f"bn_end{i}.weight"], sd[f"bn_end{i}.bias"], ll, previous, sd[f"l{i}.weight"].shape[0], last)
@@ -263,82 +335,6 @@ class HGFilterEncoder:
             if not last:
                 previous = previous + self._miopen(f"bl{i}", ll, sd[f"bl{i}.weight"], sd[f"bl{i}.bias"]) + self._miopen(f"al{i}", out, sd[f"al{i}.weight"], sd[f"al{i}.bias"])
         return outputs, tmpx, normx
-
-
-@dataclasses.dataclass(eq=False, slots=True)
-class _Packed:
-    """one packed forward handle and the leaf pair it was packed from"""
-    handle: object          # ctypes.c_void_p
-    version: object         # (weight version, bias version) when it was packed; None = repack at the next use
-    kind: int               # REPACK_*
-    weight: torch.Tensor
-    bias: object            # leaf or None
-    on_host: bool           # packed on the host (vt_*_create): replaced, not repacked in place
-
-
-class _PackedHandles:
-    """The packed forward handles of a module's convolutions, one per (weight, bias) leaf pair.  A handle is created ONCE, on the device and straight from the leaf
-    (``vt_*_create_device``), and repacked in place (``vt_*_repack``, two launches on the current stream) when a version counter of its pair changed since it was
-    packed: no copy to the host, no synchronisation, no destroy -- the handle's address is stable for the life of the module, and ordering on the stream protects
-    the launches that still read the old packing.  ``EncoderAdam`` repacks all handles of a network in one plan and marks them current, so that the check here
-    finds nothing to do.  An update that goes round the version counters (a kernel writing through ``data_ptr()``, as ``ops.FusedAdam`` does) has to say so with
-    ``invalidate_handles()``.
-
-    ``VT_ENCODER_HOST_REPACK=1`` (``host_repack``) keeps the path this replaced, for A/B: synchronise, destroy the handle, pull the leaf to the host, pack it there
-    with ``vt_*_create`` and copy it back up, per convolution and step."""
-    host_repack = os.environ.get("VT_ENCODER_HOST_REPACK", "0") != "0"
-
-    def _init_handles(self):
-        self._handles = {}          # key -> _Packed
-
-    def _packed(self, key, kind, w, b, device):
-        import ctypes as C
-        ent = self._handles.get(key)
-        ver = (w._version, b._version if b is not None else -1)
-        if ent is not None and ent.version == ver and ent.weight is w and ent.bias is b:
-            return ent.handle
-        lib, fn = L.lib(), _HANDLE_FN[kind]
-        cout, cin = w.shape[:2]
-        bias_arg = kind != REPACK_CONV3X3
-        if ent is not None and (self.host_repack or ent.on_host):
-            torch.cuda.synchronize(device)          # launches that read the old packing may still be queued
-            getattr(lib, fn + "_destroy")(ent.handle)
-            ent = None
-        with torch.cuda.device(device):
-            if self.host_repack:
-                wh = np.ascontiguousarray(w.detach().cpu().numpy().reshape(cout, cin, -1), np.float32)
-                bh = np.ascontiguousarray(b.detach().cpu().numpy(), np.float32) if b is not None else None
-                h = C.c_void_p()
-                args = (wh.ctypes.data, bh.ctypes.data if bh is not None else None) if bias_arg else (wh.ctypes.data,)
-                L.check(getattr(lib, fn + "_create")(C.byref(h), *args, cout, cin, L.stream_ptr()))
-                ent = _Packed(h, ver, kind, w, b, True)
-            else:
-                args = (L.dptr(w.detach()), L.dptr(b.detach()) if b is not None else None) if bias_arg else (L.dptr(w.detach()),)
-                if ent is None:
-                    h = C.c_void_p()
-                    L.check(getattr(lib, fn + "_create_device")(C.byref(h), *args, cout, cin, L.stream_ptr()))
-                    ent = _Packed(h, ver, kind, w, b, False)
-                else:
-                    L.check(getattr(lib, fn + "_repack")(ent.handle, *args, L.stream_ptr()))
-                    ent.version, ent.weight, ent.bias = ver, w, b          # a replaced leaf object is the pair the handle follows from now on
-        self._handles[key] = ent
-        return ent.handle
-
-    def invalidate_handles(self):
-        """the leaves were written behind the version counters: repack every handle at its next use"""
-        for ent in self._handles.values():
-            ent.version = None
-
-    def _mark_handles_current(self):
-        for ent in self._handles.values():
-            ent.version = (ent.weight._version, ent.bias._version if ent.bias is not None else -1)
-
-    def __del__(self):
-        try:
-            for ent in getattr(self, "_handles", {}).values():
-                getattr(L.lib(), _HANDLE_FN[ent.kind] + "_destroy")(ent.handle)
-        except Exception:
-            pass
 
 
 class TrainableConvBlock(_PackedHandles):
@@ -364,11 +360,7 @@ class TrainableConvBlock(_PackedHandles):
     def from_state_dict(cls, sd, prefix="", device="cuda:0"):
         """``sd``: tensors or arrays; ``prefix`` e.g. 'image_filter.conv3.' (a leading 'module.' is stripped).  The projection's norm is read from
         'downsample.0.*' when present (the name the reference loads last), else from 'bn4.*'; both names are written by ``state_dict()``."""
-        got = {}
-        for k, v in sd.items():
-            k = k[7:] if k.startswith("module.") else k
-            if k.startswith(prefix):
-                got[k[len(prefix):]] = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).detach().to(device=device, dtype=torch.float32).contiguous().clone()
+        got = {k: _leaf(v, device) for k, v in state_dict_under(sd, prefix).items()}
         for k in cls._W + tuple(f"bn{i}.{s}" for i in (1, 2, 3) for s in ("weight", "bias")):
             if k not in got:
                 raise KeyError(f"no ConvBlock parameter '{prefix}{k}'")
@@ -382,8 +374,6 @@ class TrainableConvBlock(_PackedHandles):
             leaves["downsample.2.weight"] = got["downsample.2.weight"]
             if "bn4.weight" not in leaves:
                 raise KeyError(f"'{prefix}downsample.2.weight' without the projection's norm")
-        for t in leaves.values():
-            t.requires_grad_(True)
         return cls(leaves, device)
 
     def state_dict(self):
@@ -462,10 +452,6 @@ class TrainableHourglass:
         return self._level(self.depth, x)
 
 
-def _leaf(v, device):
-    return torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).detach().to(device=device, dtype=torch.float32).contiguous().clone().requires_grad_(True)
-
-
 class TrainableStem(_PackedHandles):
     """conv1 + bn1 + ReLU (model/HGFilters.py:120-125, 167) with the four parameters as fp32 device leaves under the keys of ``ops.STEM_PARAMS``; differentiable
     through ``ops.stem_train``."""
@@ -537,11 +523,7 @@ class TrainableHGFilter:
     @classmethod
     def from_state_dict(cls, sd, prefix="", num_stack=3, num_hourglass=2, device="cuda:0"):
         """``sd``: tensors or arrays under the reference's keys; ``prefix`` e.g. 'image_filter.' or 'triplane_encoder.' (a leading 'module.' is stripped)"""
-        own = {}
-        for k, v in sd.items():
-            k = k[7:] if k.startswith("module.") else k
-            if k.startswith(prefix):
-                own[k[len(prefix):]] = v
+        own = state_dict_under(sd, prefix)
 
         def need(k):
             if k not in own:
@@ -754,8 +736,7 @@ class SIFNetEncoder:
 
     @classmethod
     def from_state_dict(cls, sd, **kw):
-        keys = [k[7:] if k.startswith("module.") else k for k in sd]
-        return cls(sd, shared_encoder=any(k.startswith("triplane_encoder.") for k in keys), **kw)
+        return cls(sd, shared_encoder=bool(state_dict_under(sd, "triplane_encoder.")), **kw)
 
     def route_report(self):
         """convolution routes taken since construction, summed over the image and triplane encoders: {'hip7x7': n, 'hip3x3': n, 'hip1x1': n, 'miopen:<layer>': n}
@@ -849,7 +830,7 @@ class SIFNetEncoder:
                     sx = x.clone()
                     side = torch.cuda.Stream(device=x.device); side.wait_stream(torch.cuda.current_stream())
                     with torch.cuda.stream(side):
-                        self._chunk_eager(sx)              # outside the capture: weight uploads, MIOpen's kernel choice for the stem, workspaces
+                        self._chunk_eager(sx)              # outside the capture: the handles' creation (an allocation each), MIOpen's kernel choice for the stem, workspaces
                     torch.cuda.current_stream().wait_stream(side)
                     torch.cuda.synchronize(x.device)
                     g = torch.cuda.CUDAGraph()

@@ -160,10 +160,6 @@ def network_state_dict(image, tri, params):
     return out
 
 
-def _strip_module(sd):
-    return {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
-
-
 class SIFNetTrainer:
     """``Trainer.train_step`` (trainer/trainer.py:97-106) for the whole ``CHORETriplaneVisibility``: the image encoder (``.image``, Cin 5) and the shared triplane
     encoder (``.tri``, Cin 1, applied once to the 3B single-channel renders as ``SIFNetEncoder._chunk_eager`` batches them) are ``TrainableHGFilter``s, the five
@@ -182,14 +178,14 @@ class SIFNetTrainer:
 
     def __init__(self, sd, camera=None, num_stack=3, num_hourglass=2, triplane_stack=3, lr=1e-3, milestones=(), gamma=0.3, max_dist=5.0,
                  loss_weights=ops.LOSS_WEIGHTS, device="cuda:0"):
-        sd = _strip_module(sd)
+        from .encoder import EncoderAdam, TrainableHGFilter, state_dict_under
+        from .sifnet import SIFNetQuery
+        sd = state_dict_under(sd, "")
         if any(k.startswith("triplane_encoder_") for k in sd):
             raise L.VtError("SIFNetTrainer: this checkpoint holds per-view triplane encoders (triplane_encoder_0. ...); only the shared form "
                             "(triplane_encoder.) is trained here")
         if int(num_stack) != int(triplane_stack):
             raise L.VtError(f"SIFNetTrainer: {num_stack} image stacks and {triplane_stack} triplane stacks; the training query pairs them one to one")
-        from .encoder import EncoderAdam, TrainableHGFilter
-        from .sifnet import SIFNetQuery
         self.device, self.max_dist = device, float(max_dist)
         self.num_stack, self.num_hourglass = int(num_stack), int(num_hourglass)
         self.lr0, self.milestones, self.gamma, self.epoch = float(lr), tuple(milestones), float(gamma), 0
@@ -259,9 +255,8 @@ class SIFNetTrainer:
         """-> a new ``SIFNetQuery`` holding the trained decoders (packed by ``vt_sifnet_create`` as any checkpoint's) and, as ``.encoder``, a ``SIFNetEncoder`` built
         from the trained encoder weights, with this trainer's camera and loss settings.  ``images`` (B,8,H,W), when given, are encoded with the trained weights and set as its maps, so that it goes straight into
         ``validate``; without them the maps are None (the generator and the fit loops call ``filter`` themselves; the trainer keeps no input of a step alive).
-        Host traffic: the decoders are read back once here, as ``DecoderTrainer.export`` does.  The encoder weights are handed over as device tensors, but a
-        ``SIFNetEncoder`` packs its convolutions on the host at their first use (``HGFilterEncoder._handle``: one read back per convolution, about 2 x 94 in the
-        shipped configuration), which happens here when ``images`` are given and at the first ``filter`` otherwise."""
+        Host traffic: only the decoders are read back, once, as ``DecoderTrainer.export`` does.  The encoder weights are handed over as device tensors and the
+        ``SIFNetEncoder`` packs its convolutions from them on the device at their first use: here when ``images`` are given, at the first ``filter`` otherwise."""
         from .encoder import SIFNetEncoder
         from .sifnet import SIFNetQuery
         out = SIFNetQuery(self.params.to_decoders(), camera=self.camera, device=self.device)
