@@ -20,6 +20,8 @@
 #ifndef VISTRACKER_H
 #define VISTRACKER_H
 
+#include <stddef.h>     /* size_t (vt_grad_rank_mean) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -898,6 +900,23 @@ void vt_repack_plan_destroy(vt_repack_plan *plan);
 /* diagnostic only (see above) */
 int vt_repack_plan_launches(const vt_repack_plan *plan);
 int vt_repack_handle_snapshot(int kind, const void *handle, void *packed_out_dev, float *scale_out_dev, void *stream);
+
+/* ---- data-parallel training: the rank-ordered gradient mean (csrc/gradreduce.hip) ----------------------------------------------------------------------------
+ * Replaces the gradient average of torch.nn.parallel.DistributedDataParallel that the reference's Trainer.train_step relies on under "multi_gpus": true
+ * (trainer/trainer.py:97-106: loss.backward() on the DDP-wrapped model all-reduces every gradient and divides by the world size before optimizer.step()).  A ring
+ * all-reduce adds in an order that depends on the ring and its chunking; here the ranks' gradients are first GATHERED (a pure copy: RCCL all_gather, or the
+ * caller's own copies for micro-batches) and then averaged by one kernel in a fixed order:
+ *
+ *   parts: W rows of `stride` >= n floats, row r = rank r's gradient.  For every i < n
+ *   out[i] = (float)((((double)parts[0*stride+i] + parts[1*stride+i]) + ... + parts[(W-1)*stride+i]) / (double)W)
+ *
+ * added in rank order, left to right, in fp64; one fp64 division; one rounding to fp32.  `out` may be one of the rows of `parts` (in place into the local
+ * gradient): an element is read from all W rows by the one thread that then writes it.  Any other overlap of `out` with the rows is an error.  No atomics, no
+ * workspace: the same bits on every call and on every rank.  W = 1 returns the input bit for bit; scaling every input by a power of two scales the output bit for
+ * bit short of overflow and underflow; NaN and Inf propagate as IEEE addition propagates them.  Pointers are 4-byte aligned; the body moves 16 bytes per access
+ * (scalar head and tail) when stride % 4 == 0 and `out` and `parts` sit alike in their 16 bytes, as torch allocations and rows of `parts` do; scalar otherwise.
+ * VT_ERR_ARG: W < 1, stride < n, a NULL pointer with n > 0.  n = 0: VT_OK, nothing launched.  `stream`: a hipStream_t. */
+int vt_grad_rank_mean(const float *parts, int W, size_t n, size_t stride, float *out, void *stream);
 
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two

@@ -203,6 +203,7 @@ SIGNATURES = {
     "vt_repack_plan_run": (ci, [vp, vp]),
     "vt_repack_plan_destroy": (None, [vp]),
     "vt_repack_handle_snapshot": (ci, [ci, vp, fp, fp, vp]),
+    "vt_grad_rank_mean": (ci, [fp, ci, C.c_size_t, C.c_size_t, fp, vp]),             # parts, W, n, stride | out | stream
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
 }

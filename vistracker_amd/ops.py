@@ -1391,3 +1391,115 @@ class FusedAdam:
             g = g.contiguous()
             L.check(L.lib().vt_adam_step(L.dptr(p.data), L.dptr(g), L.dptr(self.m[i]), L.dptr(self.v[i]), p.numel(), self.t, self.lrs[i],
                                          self.betas[0], self.betas[1], self.eps, L.dptr(self.stop_flag), L.stream_ptr()))
+
+
+# --------------------------------------------------------------------------------------------------
+# Data-parallel training: the rank-ordered gradient mean
+# --------------------------------------------------------------------------------------------------
+def grad_rank_mean(parts, out=None):
+    """``vt_grad_rank_mean``: ``parts`` (W, n) float32 on the device, row r = rank r's gradient; the rows may be ``stride`` >= n apart (a (W, n) view of a
+    (W, stride) tensor: ``parts.stride(0)`` is passed on).  -> ``out`` (n,), default a new tensor: the rows added in rank order in fp64, divided by W once, rounded
+    to fp32 once.  ``out`` may be one of the rows (in place).  The same bits on every call."""
+    if not (torch.is_tensor(parts) and parts.is_cuda and parts.dtype == torch.float32 and parts.dim() == 2):
+        raise L.VtError("grad_rank_mean: parts is a (W, n) float32 device tensor")
+    W, n = parts.shape
+    stride = parts.stride(0) if W > 1 else max(parts.stride(0), n)
+    if n > 1 and parts.stride(1) != 1:
+        raise L.VtError("grad_rank_mean: the rows of parts must be contiguous")
+    with torch.cuda.device(parts.device):
+        if out is None:
+            out = torch.empty(n, device=parts.device)
+        if not (torch.is_tensor(out) and out.device == parts.device and out.dtype == torch.float32 and out.numel() == n and out.is_contiguous()):
+            raise L.VtError(f"grad_rank_mean: out is a contiguous float32 tensor of {n} values on {parts.device}")
+        L.check(L.lib().vt_grad_rank_mean(parts.data_ptr() if n else None, W, n, stride, out.data_ptr() if n else None, L.stream_ptr()))
+    return out
+
+
+class RankMean:
+    """The gradient average of a data-parallel step over flat gradient buffers, with the same bits on every rank: the ranks' buffers are GATHERED (a pure copy) into
+    one (W, n_k) workspace per buffer, allocated once at the first use, and ``vt_grad_rank_mean`` adds the rows in rank order in fp64 into the buffer itself.
+
+        rm = RankMean([enc_opt.grad, tri_opt.grad, params.flat], group)       # the tensors give sizes and device; reduce() may be handed others of the same sizes
+        loss.backward(); rm.reduce(); optimiser steps
+
+    ``group``: a ``torch.distributed`` process group, ``True`` for the default group, ``None`` for no group (a world of one).
+    * RCCL ("nccl"): ``dist.all_gather_into_tensor`` on the current stream, no host wait.
+    * gloo: the gather goes through host copies, as ``sharding.gather_params`` and ``reduce_rows_exact`` do.  TEST ONLY: it synchronises; it exists so that several
+      ranks can share the one GPU of a test box.
+    * a world of one: the gather is a copy (``VT_FORCE_DIST=1``: the collective runs all the same, as in ``sharding.gather_params``).
+    ``reduce_local(parts)`` runs the same kernel over rows the caller filled itself (``rows(M)``: M rows per buffer, allocated once per M): micro-batches."""
+
+    def __init__(self, buffers, group=None):
+        import os
+        buffers = list(buffers)
+        if not buffers or any(not (torch.is_tensor(b) and b.is_cuda and b.dtype == torch.float32 and b.dim() == 1 and b.is_contiguous()) for b in buffers):
+            raise L.VtError("RankMean: flat contiguous float32 device buffers expected")
+        self.buffers, self.device = buffers, buffers[0].device
+        self.sizes = [b.numel() for b in buffers]
+        self.group, self.world, self.rank, self.backend = None, 1, 0, None
+        if group is not None and group is not False:
+            import torch.distributed as dist
+            if not (dist.is_available() and dist.is_initialized()):
+                raise L.VtError("RankMean: a process group was asked for, but torch.distributed is not initialised")
+            self.group = dist.group.WORLD if group is True else group
+            self.world, self.rank, self.backend = dist.get_world_size(self.group), dist.get_rank(self.group), dist.get_backend(self.group)
+            if self.backend not in ("nccl", "gloo"):
+                raise L.VtError(f"RankMean: backend {self.backend!r}; nccl (RCCL) or gloo expected")
+        self.collective = self.group is not None and (self.world > 1 or os.environ.get("VT_FORCE_DIST") == "1")
+        self._rows = {}
+
+    @property
+    def workspaces(self):
+        """the (W, n_k) gather workspaces, allocated at the first ``reduce`` (a trainer without a group never pays for them)"""
+        return self.rows(self.world)
+
+    def rows(self, M):
+        """one (M, n_k) float32 workspace per buffer, allocated at the first call for this M"""
+        M = int(M)
+        if M < 1:
+            raise L.VtError("RankMean.rows: at least one row")
+        if M not in self._rows:
+            with torch.cuda.device(self.device):
+                self._rows[M] = [torch.empty(M, n, device=self.device) for n in self.sizes]
+        return self._rows[M]
+
+    def gather(self, t, out=None):
+        """``t`` (any shape and dtype, on the device, the same on every rank) from every rank of the group -> (W, *t.shape) in rank order"""
+        t = t.contiguous()
+        if out is None:
+            out = torch.empty((self.world,) + tuple(t.shape), dtype=t.dtype, device=t.device)
+        if not self.collective:
+            out[0].copy_(t)
+            return out
+        import torch.distributed as dist
+        if self.backend == "gloo":                                 # test only: no device collectives, host copies either side
+            host = torch.empty(out.shape, dtype=t.dtype)
+            dist.all_gather(list(host.unbind(0)), t.cpu(), group=self.group)
+            out.copy_(host)
+        else:
+            dist.all_gather_into_tensor(out.view(-1), t.view(-1), group=self.group)
+        return out
+
+    def _check(self, buffers):
+        buffers = self.buffers if buffers is None else list(buffers)
+        if len(buffers) != len(self.sizes) or any(not torch.is_tensor(b) or b.numel() != n or b.device != self.device for b, n in zip(buffers, self.sizes)):
+            raise L.VtError(f"RankMean: {len(self.sizes)} buffers of {self.sizes} values on {self.device} expected")
+        return buffers
+
+    def reduce(self, buffers=None):
+        """every buffer (default: those of the constructor) becomes the mean over the group's ranks, in place; all ranks call it, with the same sizes"""
+        buffers = self._check(buffers)
+        for b, ws in zip(buffers, self.workspaces):
+            self.gather(b, out=ws)
+            grad_rank_mean(ws, out=b)
+        return buffers
+
+    def reduce_local(self, parts, buffers=None):
+        """``parts``: one (M, n_k) tensor per buffer (``rows(M)``), filled by the caller; every buffer becomes the mean of its M rows, in row order"""
+        buffers = self._check(buffers)
+        parts = list(parts)
+        if len(parts) != len(buffers) or any(p.dim() != 2 or p.shape[1] != n or p.shape[0] != parts[0].shape[0] for p, n in zip(parts, self.sizes)):
+            raise L.VtError(f"RankMean.reduce_local: one (M, n) tensor per buffer expected, n = {self.sizes}")
+        for b, p in zip(buffers, parts):
+            grad_rank_mean(p, out=b)
+        return buffers

@@ -138,6 +138,38 @@ class DecoderTrainer:
         return out
 
 
+def slice_batch(batch, sl):
+    """the frames ``sl`` (a slice, or an index tensor / list) of a labelled batch: every entry of ``make_training_batch``'s dict carries the frame axis first"""
+    return {k: v[sl] for k, v in batch.items()}
+
+
+def distributed_indices(num_items, world, rank, epoch, seed=0, shuffle=True, drop_last=True):
+    """this rank's item indices for an epoch: ``list(torch.utils.data.distributed.DistributedSampler(range(num_items), num_replicas=world, rank=rank,
+    shuffle=shuffle, seed=seed, drop_last=drop_last))`` after ``set_epoch(epoch)``, index for index -- the permutation of ``torch.randperm`` under
+    ``manual_seed(seed + epoch)``, cut to (``drop_last``, as data/base_data.py ``get_loader`` sets it) or padded by repetition to a multiple of ``world``, then
+    every ``world``-th item from ``rank`` on.  A host function, as ``multistep_lr``."""
+    num_items, world, rank = int(num_items), int(world), int(rank)
+    if world < 1 or not 0 <= rank < world:
+        raise L.VtError(f"distributed_indices: rank {rank} of {world}")
+    if shuffle:
+        g = torch.Generator()
+        g.manual_seed(int(seed) + int(epoch))
+        idx = torch.randperm(num_items, generator=g).tolist()
+    else:
+        idx = list(range(num_items))
+    if drop_last and num_items % world != 0:
+        per_rank = -(-(num_items - world) // world)
+    else:
+        per_rank = -(-num_items // world)
+    total = per_rank * world
+    if drop_last:
+        idx = idx[:total]
+    elif total > len(idx):
+        pad = total - len(idx)
+        idx = idx + (idx[:pad] if pad <= len(idx) else (idx * -(-pad // len(idx)))[:pad])
+    return idx[rank:total:world]
+
+
 def multistep_lr(lr0, milestones, gamma, epoch):
     """``torch.optim.lr_scheduler.MultiStepLR(milestones, gamma)`` as a function of the epoch counter: lr0 . gamma^(number of milestones <= epoch), multiplied up
     milestone by milestone as the scheduler does, so the value is the scheduler's to the last bit (a milestone listed k times counts k times)."""
@@ -177,7 +209,7 @@ class SIFNetTrainer:
     (``triplane_encoder_0.`` ...) raise.  The query needs as many triplane stacks as image stacks (chore_triplane.py:146-147 indexes both with one counter)."""
 
     def __init__(self, sd, camera=None, num_stack=3, num_hourglass=2, triplane_stack=3, lr=1e-3, milestones=(), gamma=0.3, max_dist=5.0,
-                 loss_weights=ops.LOSS_WEIGHTS, device="cuda:0"):
+                 loss_weights=ops.LOSS_WEIGHTS, device="cuda:0", group=None):
         from .encoder import EncoderAdam, TrainableHGFilter, state_dict_under
         from .sifnet import SIFNetQuery
         sd = state_dict_under(sd, "")
@@ -198,6 +230,12 @@ class SIFNetTrainer:
         self.image_optimizer, self.tri_optimizer = EncoderAdam(self.image, lr=lr), EncoderAdam(self.tri, lr=lr)
         self.optimizer = ops.FusedAdam([self.params.flat], lr=lr)
         self.set_step(0)
+        # the three flat gradient buffers of the network (the decoders' is the one autograd makes anew every step: handed to the reducer per call)
+        self.reducer = ops.RankMean([self.image_optimizer.grad, self.tri_optimizer.grad, self.params.flat.detach()], group)
+        self.group = self.reducer.group
+        if self.group is not None and not self.in_sync():
+            raise L.VtError(f"SIFNetTrainer: rank {self.reducer.rank} of {self.reducer.world} was built from weights that differ from another rank's; "
+                            "data-parallel steps need the same parameters and moments on every rank")
 
     @property
     def lr(self):
@@ -233,18 +271,78 @@ class SIFNetTrainer:
             maps.append(ops.FeatureMaps(d))
         return maps
 
-    def train_step(self, batch, images, crop_center):
-        """one step on a batch of ``make_training_batch`` and its (B,8,H,W) network input: zero_grad, both encoder forwards, the S per-stack ``FeatureMaps``,
-        ``query_train`` over all stacks, ``get_errors``, one ``error.backward()`` (decoders, then both encoders, through the maps), the three optimiser steps.
-        -> (error (), losses_all (6,)): float64 device tensors of the objective BEFORE the update; nothing here waits on the host."""
+    def backward(self, batch, images, crop_center):
+        """the gradient half of a step on a batch of ``make_training_batch`` and its (B,8,H,W) network input: zero_grad, both encoder forwards, the S per-stack
+        ``FeatureMaps``, ``query_train`` over all stacks, ``get_errors``, one ``error.backward()`` (decoders, then both encoders, through the maps).
+        -> (error (), losses_all (6,)): float64 device tensors of the objective; the gradients lie in ``flat_grads()``; nothing here waits on the host."""
         self.image_optimizer.zero_grad(); self.tri_optimizer.zero_grad(); self.optimizer.zero_grad()
         maps = self.forward(images)
         self.net.query_train(self.params, batch["points"], crop_center=crop_center, body_center=batch["body_center"], maps=maps)
         error, losses_all = self.net.get_errors(batch["df_h"], batch["df_o"], batch["labels"], batch["pca_axis"], self.max_dist, batch["body_center"],
                                                 batch["obj_center"], visibility=batch["visibility"])
         error.backward()
-        self.image_optimizer.step(); self.tri_optimizer.step(); self.optimizer.step()
         return error.detach(), losses_all
+
+    def apply(self):
+        """the three optimiser steps on whatever the gradient buffers hold"""
+        self.image_optimizer.step(); self.tri_optimizer.step(); self.optimizer.step()
+
+    def flat_grads(self):
+        """the three flat gradient buffers after a ``backward``: image encoder, triplane encoder, decoders.  An encoder leaf whose ``.grad`` autograd replaced is
+        copied into its flat buffer first (``EncoderAdam.step`` does the same); a leaf without a gradient holds zeros there and is skipped by ``step`` as before."""
+        self.image_optimizer._bind_grads(copy=True); self.tri_optimizer._bind_grads(copy=True)
+        return [self.image_optimizer.grad, self.tri_optimizer.grad, self.params.flat.grad]
+
+    def train_step(self, batch, images, crop_center):
+        """one step on a batch of ``make_training_batch`` and its (B,8,H,W) network input: ``backward`` then ``apply``.  With a process group (``group=`` of the
+        constructor) every rank calls it on ITS frames and the three flat gradient buffers become the mean over the ranks in between (``ops.RankMean.reduce``:
+        gather, then a rank-ordered fp64 sum), as ``DistributedDataParallel`` leaves every leaf's ``.grad``, but with the same bits on every rank.
+        -> (error (), losses_all (6,)): float64 device tensors of THIS rank's objective BEFORE the update; nothing here waits on the host (over RCCL; a gloo
+        group, the single-GPU dry run of the tests, goes through host copies)."""
+        error, losses_all = self.backward(batch, images, crop_center)
+        if self.group is not None:
+            self.reducer.reduce(self.flat_grads())
+        self.apply()
+        return error, losses_all
+
+    def train_step_micro(self, micro_batches):
+        """one step whose gradient is the mean over micro-batches: a list of ``(batch, images, crop_center)`` with the same number of frames each (a B = 16 step
+        taken as 2 x 8 when the activations of 16 frames do not fit).  Every micro-batch runs ``backward``; its three flat gradients are copied into row k of a
+        workspace; ``vt_grad_rank_mean`` averages the rows in order into the flat gradients; with a group the result is then averaged over the ranks; one ``apply``.
+        M micro-batches on one rank give the bits of M ranks with one of them each.  -> (errors (M,), losses_all (M, 6)); no host wait."""
+        micro_batches = list(micro_batches)
+        if not micro_batches:
+            raise L.VtError("train_step_micro: no micro-batch")
+        frames = [int(images.shape[0]) for _, images, _ in micro_batches]
+        if len(set(frames)) != 1:
+            raise L.VtError(f"train_step_micro: micro-batches of {frames} frames; the mean of their gradients is the gradient of the whole only for equal sizes")
+        rows = self.reducer.rows(len(micro_batches))
+        errors, losses = [], []
+        for k, (batch, images, crop_center) in enumerate(micro_batches):
+            error, losses_all = self.backward(batch, images, crop_center)
+            for ws, g in zip(rows, self.flat_grads()):
+                ws[k].copy_(g)
+            errors.append(error); losses.append(losses_all)
+        grads = self.reducer.reduce_local(rows, self.flat_grads())
+        if self.group is not None:
+            self.reducer.reduce(grads)
+        self.apply()
+        return torch.stack(errors), torch.stack(losses)
+
+    def in_sync(self):
+        """whether every rank of the group holds the same parameters and Adam moments: the three parameter buffers and the six moment buffers are each reduced to
+        one integer on the device (the int32 view summed in int64), the nine numbers are gathered over the group and compared.  One small collective and ONE
+        read-back: for epoch boundaries and tests, never inside ``train_step``.  Without a group: True."""
+        if self.group is None:
+            return True
+        bufs = []
+        for o in (self.image_optimizer, self.tri_optimizer):
+            bufs += [o.flat, o.m, o.v]
+        bufs += [self.params.flat.detach(), self.optimizer.m[0], self.optimizer.v[0]]
+        with torch.cuda.device(self.reducer.device):
+            sums = torch.stack([b.view(torch.int32).sum(dtype=torch.int64) for b in bufs])
+            rows = self.reducer.gather(sums)
+            return bool((rows == rows[0:1]).all().item())
 
     def state_dict(self):
         """the whole network under the reference's checkpoint keys (``image_filter.*``, ``triplane_encoder.*``, ``df.0.weight`` ...); device copies.  It loads
