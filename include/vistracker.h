@@ -918,6 +918,51 @@ int vt_repack_handle_snapshot(int kind, const void *handle, void *packed_out_dev
  * VT_ERR_ARG: W < 1, stride < n, a NULL pointer with n > 0.  n = 0: VT_OK, nothing launched.  `stream`: a hipStream_t. */
 int vt_grad_rank_mean(const float *parts, int W, size_t n, size_t stride, float *out, void *stream);
 
+/* ---- the gradient record and the non-finite step guard (gradstat.hip) -----------------------------------------------------------------------------------------
+ * The reference's train_step runs under torch.autograd.set_detect_anomaly(True) (trainer/trainer.py:97-106): a NaN in its backward stops the run.  Here the step
+ * has no host wait, so the decision is taken on the device: the gradients are measured per tensor, the step is closed by one small launch that decides whether it
+ * is skipped and how far it is clipped, and the optimiser kernels take that decision as their stop flag (vt_adam_step's `stop_flag`).  After vt_grad_rank_mean
+ * every rank holds the same gradient bits, so every rank takes the same decision with no collective.
+ *
+ * vt_grad_stats: `g` holds n floats; `seg_off` holds 2 * n_seg ascending offsets into it: segment s is [seg_off[2s], seg_off[2s+1]), and what lies between the end
+ * of one segment and the start of the next (the 64-float padding of the encoders' flat buffers), before the first or after the last belongs to no segment and is
+ * not read into any result.  (Begin / end pairs and not n_seg + 1 boundaries: boundaries alone cannot leave a gap out.)  Per segment:
+ *   nonfinite[s] = the number of NaN or +-Inf elements
+ *   sumsq[s]     = the sum of g^2 over the FINITE elements, each squared in fp64 (exact) and added in fp64: a NaN does not erase the norm of its tensor
+ *   maxabs[s]    = the largest |g| over the finite elements, 0 for none
+ * Denormals count with their value.  No atomics; the order of the additions is fixed by the element's index in its segment alone (chunks of VT_GRAD_STATS_CHUNK
+ * elements from the segment's start, one wave each, finished in chunk order), so the bits are the same on every call, on every rank, and wherever the buffer
+ * lies.  Loads are 16 bytes per lane where a chunk starts on a 16-byte boundary.  Offsets are clamped into [0, n]; a table that is not ascending gives
+ * meaningless results, never a read out of bounds.  `ws`: vt_grad_stats_workspace_bytes(n, n_seg) bytes, 8-byte aligned.  Three launches.
+ *
+ * vt_grad_guard_close: closes a step from the results of up to three vt_grad_stats calls (a buffer that is not used: n_seg = 0).
+ *   total = all sumsq added in index order, buffer after buffer, in fp64;  norm = sqrt(total)
+ *   skip  = any nonfinite[] > 0, or *error (a device double, may be NULL) is NaN or +-Inf
+ *   coef  = max_norm > 0 ? (float)min(1.0, max_norm / (norm + 1e-6)) : 1.f        (torch's clip_grad_norm_, evaluated in fp64 and rounded once)
+ * `record` (device, 8-byte aligned, vt_grad_guard_record_bytes(n_seg_total, ring) bytes, zeroed once by the caller):
+ *   long steps @0, long skipped @8 (both advanced by this call), then 1 + ring slots of VT_GUARD_SLOT_HEAD + 16 * n_seg_total bytes each: slot 0 is the last
+ *   step, slot 1 + steps % ring (steps before this call) the ring's.  A slot: double norm @VT_GUARD_NORM, double error @VT_GUARD_ERROR, float coef @VT_GUARD_COEF,
+ *   int skip @VT_GUARD_SKIP, long step @VT_GUARD_STEP, then double sumsq[n_seg_total], float maxabs[n_seg_total], int nonfinite[n_seg_total].
+ *   record + VT_GUARD_HEAD + VT_GUARD_SKIP is the stop flag of the optimiser launches, record + VT_GUARD_HEAD + VT_GUARD_COEF the factor of vt_grad_scale.
+ *
+ * vt_grad_scale: g[i] *= *coef in place, one fp32 multiplication per element; nothing is written when *skip is set (NULL: never) or *coef is 1. */
+#define VT_GRAD_STATS_CHUNK 4096
+#define VT_GUARD_HEAD 16
+#define VT_GUARD_SLOT_HEAD 32
+#define VT_GUARD_NORM 0
+#define VT_GUARD_ERROR 8
+#define VT_GUARD_COEF 16
+#define VT_GUARD_SKIP 20
+#define VT_GUARD_STEP 24
+long vt_grad_stats_workspace_bytes(long n, int n_seg);
+int vt_grad_stats(const float *g, long n, const long *seg_off, int n_seg, double *sumsq, float *maxabs, int *nonfinite, void *ws, void *stream);
+long vt_grad_guard_record_bytes(int n_seg_total, int ring);
+int vt_grad_guard_close(const double *sumsq0, const float *maxabs0, const int *nonfinite0, int n_seg0,
+                        const double *sumsq1, const float *maxabs1, const int *nonfinite1, int n_seg1,
+                        const double *sumsq2, const float *maxabs2, const int *nonfinite2, int n_seg2,
+                        const double *error, double max_norm, void *record, int ring, void *stream);
+int vt_grad_scale(float *g, long n, const float *coef, const int *skip, void *stream);
+
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two
  * workgroups of 256 threads per CU, non-trivial operands), out[1] = shader clock sustained during it (MHz: s_memtime against the 100 MHz s_memrealtime),

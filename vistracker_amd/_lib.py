@@ -204,6 +204,11 @@ SIGNATURES = {
     "vt_repack_plan_destroy": (None, [vp]),
     "vt_repack_handle_snapshot": (ci, [ci, vp, fp, fp, vp]),
     "vt_grad_rank_mean": (ci, [fp, ci, C.c_size_t, C.c_size_t, fp, vp]),             # parts, W, n, stride | out | stream
+    "vt_grad_stats_workspace_bytes": (cl, [cl, ci]),
+    "vt_grad_stats": (ci, [fp, cl, fp, ci, fp, fp, fp, fp, vp]),                      # g, n, seg_off (2 n_seg), n_seg | sumsq, maxabs, nonfinite | ws | stream
+    "vt_grad_guard_record_bytes": (cl, [ci, ci]),
+    "vt_grad_guard_close": (ci, [fp, fp, fp, ci] * 3 + [fp, cd, fp, ci, vp]),          # 3 x (sumsq, maxabs, nonfinite, n_seg) | error, max_norm, record, ring | stream
+    "vt_grad_scale": (ci, [fp, cl, fp, fp, vp]),                                      # g, n, coef, skip | stream
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
 }

@@ -70,6 +70,22 @@ static inline int vt_upload(T **dst, const T *host, size_t n, hipStream_t st)
     return VT_OK;
 }
 
+// the CU count of the current device, asked once per device (grid caps of the streaming kernels: gradreduce.hip, gradstat.hip)
+static inline int vt_cu_count(int *cus)
+{
+    static std::atomic<int> cached[64];
+    int dev = 0;
+    VT_HIP(hipGetDevice(&dev));
+    int c = cached[dev & 63].load(std::memory_order_acquire);
+    if (c <= 0) {
+        VT_HIP(hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev));
+        if (c <= 0) c = 1;
+        cached[dev & 63].store(c, std::memory_order_release);
+    }
+    *cus = c;
+    return VT_OK;
+}
+
 // wave64 sum via DPP-free shuffles
 __device__ __forceinline__ float wave_sum(float v)
 {

@@ -112,22 +112,6 @@ __global__ __launch_bounds__(THREADS) void mean_kernel(const float *parts, int W
     }
 }
 
-// the CU count of a device, asked once per device
-static int cu_count(int *cus)
-{
-    static std::atomic<int> cached[64];
-    int dev = 0;
-    VT_HIP(hipGetDevice(&dev));
-    int c = cached[dev & 63].load(std::memory_order_acquire);
-    if (c <= 0) {
-        VT_HIP(hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev));
-        if (c <= 0) c = 1;
-        cached[dev & 63].store(c, std::memory_order_release);
-    }
-    *cus = c;
-    return VT_OK;
-}
-
 }  // namespace grm
 
 extern "C" int vt_grad_rank_mean(const float *parts, int W, size_t n, size_t stride, float *out, void *stream)
@@ -154,7 +138,7 @@ extern "C" int vt_grad_rank_mean(const float *parts, int W, size_t n, size_t str
         if (nvec == 0) head = n;
     }
     int cus = 0;
-    if (int rc = grm::cu_count(&cus)) return rc;
+    if (int rc = vt_cu_count(&cus)) return rc;
     const size_t nscalar = n - 4 * nvec;
     const size_t work = nvec > nscalar ? nvec : nscalar;
     size_t blocks = (work + grm::THREADS - 1) / grm::THREADS;

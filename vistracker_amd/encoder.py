@@ -697,7 +697,10 @@ class EncoderAdam:
         self.grad.zero_()
         self._bind_grads(copy=False)
 
-    def step(self):
+    def step(self, skip=None):
+        """``skip``: a device int32 tensor of one value (``ops.StepGuard.close``), the stop flag of the Adam launch of this step: when it is set, ``flat``, ``m`` and
+        ``v`` are left untouched.  ``t`` advances all the same (the host cannot know the outcome without waiting: a skipped step costs one step of bias
+        correction) and the repack plan still runs: it packs the unchanged weights to the same bytes."""
         for p, pv in zip(self.params, self._pviews):
             if p.data_ptr() != pv.data_ptr():
                 raise L.VtError("EncoderAdam.step: a parameter's .data was replaced since the optimiser was built; the flat buffer and the repack plan still point at the old storage")
@@ -713,7 +716,7 @@ class EncoderAdam:
                 sl = slice(self._offs[i], self._offs[i] + self.params[i].numel())
                 keep.append((sl, self.flat[sl].clone(), self.m[sl].clone(), self.v[sl].clone()))
             L.check(L.lib().vt_adam_step(L.dptr(self.flat), L.dptr(self.grad), L.dptr(self.m), L.dptr(self.v), self.n, self.t, self.lr, self.betas[0], self.betas[1],
-                                         self.eps, None, L.stream_ptr()))
+                                         self.eps, L.dptr(skip), L.stream_ptr()))
             for sl, p0, m0, v0 in keep:
                 self.flat[sl].copy_(p0); self.m[sl].copy_(m0); self.v[sl].copy_(v0)
             L.check(L.lib().vt_repack_plan_run(self._plan, L.stream_ptr()))

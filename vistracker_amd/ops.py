@@ -1382,15 +1382,19 @@ class FusedAdam:
         for p in self.params:
             p.grad = None
 
-    def step(self, grads=None):
+    def step(self, grads=None, skip=None):
+        """``skip``: a device int32 tensor of one value (``StepGuard.close``) handed to the kernel as its stop flag for this step: when it is set, parameters and
+        both moments are left untouched.  The host counter ``t`` advances all the same -- the host cannot know the outcome without waiting -- so a skipped step
+        costs one step of bias correction and nothing else."""
         self.t += 1
+        stop = self.stop_flag if skip is None else skip
         for i, p in enumerate(self.params):
             g = p.grad if grads is None else grads[i]
             if g is None:
                 continue
             g = g.contiguous()
             L.check(L.lib().vt_adam_step(L.dptr(p.data), L.dptr(g), L.dptr(self.m[i]), L.dptr(self.v[i]), p.numel(), self.t, self.lrs[i],
-                                         self.betas[0], self.betas[1], self.eps, L.dptr(self.stop_flag), L.stream_ptr()))
+                                         self.betas[0], self.betas[1], self.eps, L.dptr(stop), L.stream_ptr()))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1503,3 +1507,153 @@ class RankMean:
         for b, p in zip(buffers, parts):
             grad_rank_mean(p, out=b)
         return buffers
+
+
+# --------------------------------------------------------------------------------------------------
+# The gradient record and the non-finite step guard
+# --------------------------------------------------------------------------------------------------
+GRAD_STATS_CHUNK = 4096                                        # VT_GRAD_STATS_CHUNK (include/vistracker.h)
+_GUARD_HEAD, _GUARD_SLOT_HEAD, _GUARD_COEF, _GUARD_SKIP = 16, 32, 16, 20      # VT_GUARD_* (include/vistracker.h)
+
+
+def _seg_table(seg_off, n, device, what):
+    """(n_seg, 2) begin / end offsets, ascending and inside [0, n], as an int64 device tensor; a host list is checked, a device tensor is the caller's"""
+    if torch.is_tensor(seg_off) and seg_off.is_cuda:
+        if seg_off.dtype != torch.int64 or seg_off.dim() != 2 or seg_off.shape[1] != 2 or not seg_off.is_contiguous() or seg_off.device != device:
+            raise L.VtError(f"{what}: seg_off is a contiguous (n_seg, 2) int64 tensor on {device}")
+        return seg_off
+    a = np.asarray(seg_off, dtype=np.int64).reshape(-1, 2)
+    flat = a.reshape(-1)
+    if flat.size and (flat[0] < 0 or flat[-1] > n or (np.diff(flat) < 0).any()):
+        raise L.VtError(f"{what}: the segments' begin / end offsets must ascend inside [0, {n}]")
+    return torch.as_tensor(a, device=device)
+
+
+def grad_stats(g, seg_off, ws=None, out=None):
+    """``vt_grad_stats``: ``g`` a flat float32 device tensor, ``seg_off`` (n_seg, 2) begin / end offsets into it (a list, or an int64 device tensor), ascending;
+    what lies between two segments belongs to none.  -> (sumsq (n_seg,) float64, maxabs (n_seg,) float32, nonfinite (n_seg,) int32) on the device: per segment
+    the fp64 sum of squares and the largest magnitude of the FINITE elements, and the number of NaN / Inf.  The same bits on every call.  ``ws`` (uint8,
+    ``vt_grad_stats_workspace_bytes``) and ``out`` (the three tensors) may be handed in to save the allocations.  No host wait."""
+    if not (torch.is_tensor(g) and g.is_cuda and g.dtype == torch.float32 and g.dim() == 1 and g.is_contiguous()):
+        raise L.VtError("grad_stats: g is a flat contiguous float32 device tensor")
+    n = g.numel()
+    with torch.cuda.device(g.device):
+        seg = _seg_table(seg_off, n, g.device, "grad_stats")
+        n_seg = seg.shape[0]
+        if out is None:
+            out = (torch.zeros(n_seg, dtype=torch.float64, device=g.device), torch.zeros(n_seg, device=g.device),
+                   torch.zeros(n_seg, dtype=torch.int32, device=g.device))
+        need = int(L.lib().vt_grad_stats_workspace_bytes(n, n_seg))
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=g.device)
+        if ws.numel() < need or ws.device != g.device:
+            raise L.VtError(f"grad_stats: a workspace of {need} bytes on {g.device} expected")
+        if n_seg:
+            L.check(L.lib().vt_grad_stats(g.data_ptr(), n, seg.data_ptr(), n_seg, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), ws.data_ptr(),
+                                          L.stream_ptr()))
+    return out
+
+
+def grad_scale(g, coef, skip=None):
+    """``vt_grad_scale``: ``g[i] *= coef[0]`` in place (one fp32 multiplication per element) unless ``skip[0]`` is set; ``coef`` float32 and ``skip`` int32 device
+    tensors of one value"""
+    with torch.cuda.device(g.device):
+        L.check(L.lib().vt_grad_scale(L.dptr(g), g.numel(), L.dptr(coef), L.dptr(skip), L.stream_ptr()))
+    return g
+
+
+class StepGuard:
+    """The gradient record and the non-finite guard of a training step over up to three flat gradient buffers, decided on the device.
+
+        guard = StepGuard([enc_opt.grad, tri_opt.grad, params.flat], segments, names, max_norm=1.0, record=8)
+        loss.backward(); skip = guard.close(grads, loss); opt.step(skip=skip) ...
+        guard.read()                                # epoch boundaries: the one method that waits on the host
+
+    ``segments[k]``: the (offset, length) of every tensor in buffer k, ascending and disjoint (padding between them belongs to no segment); ``names[k]`` their
+    names.  ``close`` measures every buffer (``vt_grad_stats``), closes the step (``vt_grad_guard_close``: the step is SKIPPED when any element of a segment or
+    the error is NaN / Inf; ``max_norm``: torch's ``clip_grad_norm_`` coefficient from the global norm of the finite elements) and, with ``max_norm``, scales
+    the buffers in place (``vt_grad_scale``; not on a skipped step).  -> the device int32 ``skip``, the ``stop_flag`` of the optimiser launches.  Offsets,
+    workspaces, results and the record are allocated here once; ``record`` = K keeps the last K steps in a ring.  Computed from buffers that every rank holds
+    identically (after ``RankMean.reduce``), the decision is the same on every rank with no collective."""
+
+    def __init__(self, buffers, segments, names, max_norm=None, record=0):
+        buffers, segments, names = list(buffers), [list(s) for s in segments], [list(n) for n in names]
+        if not 1 <= len(buffers) <= 3 or len(segments) != len(buffers) or len(names) != len(buffers):
+            raise L.VtError("StepGuard: one to three buffers, with one list of segments and one of names each")
+        if any(not (torch.is_tensor(b) and b.is_cuda and b.dtype == torch.float32 and b.dim() == 1) for b in buffers):
+            raise L.VtError("StepGuard: flat float32 device buffers expected")
+        self.device, self.sizes = buffers[0].device, [b.numel() for b in buffers]
+        self.max_norm = None if max_norm is None else float(max_norm)
+        if self.max_norm is not None and not self.max_norm > 0:
+            raise L.VtError(f"StepGuard: max_norm {max_norm}; a positive norm, or None for no clipping")
+        self.ring = int(record)
+        if self.ring < 0:
+            raise L.VtError(f"StepGuard: record {record}; the number of steps kept, 0 for the last one only")
+        self.names = [str(x) for ns in names for x in ns]
+        if len(set(self.names)) != len(self.names):
+            raise L.VtError("StepGuard: the names must differ")
+        lib = L.lib()
+        with torch.cuda.device(self.device):
+            self._seg, self._out, self._ws = [], [], []
+            for k, (n, segs, ns) in enumerate(zip(self.sizes, segments, names)):
+                if len(segs) != len(ns):
+                    raise L.VtError(f"StepGuard: buffer {k} has {len(segs)} segments and {len(ns)} names")
+                table = [(int(o), int(o) + int(l)) for o, l in segs]
+                if any(e < b for b, e in table):
+                    raise L.VtError(f"StepGuard: buffer {k} has a segment of negative length")
+                self._seg.append(_seg_table(table, n, self.device, f"StepGuard: buffer {k}"))
+                self._out.append((torch.zeros(len(segs), dtype=torch.float64, device=self.device), torch.zeros(len(segs), device=self.device),
+                                  torch.zeros(len(segs), dtype=torch.int32, device=self.device)))
+                self._ws.append(torch.empty(int(lib.vt_grad_stats_workspace_bytes(n, len(segs))), dtype=torch.uint8, device=self.device))
+            self.n_seg = len(self.names)
+            self._slot = _GUARD_SLOT_HEAD + 16 * self.n_seg
+            self.record = torch.zeros(int(lib.vt_grad_guard_record_bytes(self.n_seg, self.ring)) // 8, dtype=torch.int64, device=self.device)
+            raw = self.record.view(torch.uint8)
+            self.coef = raw[_GUARD_HEAD + _GUARD_COEF:_GUARD_HEAD + _GUARD_COEF + 4].view(torch.float32)
+            self.skip = raw[_GUARD_HEAD + _GUARD_SKIP:_GUARD_HEAD + _GUARD_SKIP + 4].view(torch.int32)
+        self.launches_per_close = 3 * len(buffers) + 1 + (len(buffers) if self.max_norm is not None else 0)
+
+    def close(self, grads, error=None):
+        """``grads``: one flat float32 tensor per buffer of the constructor, of its size; ``error``: the step's objective, a float64 device scalar, or None.
+        -> ``skip``, a device int32 tensor of one value (the same tensor every call).  Nothing here waits on the host."""
+        grads = list(grads)
+        if len(grads) != len(self.sizes) or any(not torch.is_tensor(g) or g.numel() != n or g.device != self.device or g.dtype != torch.float32
+                                                 for g, n in zip(grads, self.sizes)):
+            raise L.VtError(f"StepGuard.close: {len(self.sizes)} float32 buffers of {self.sizes} values on {self.device} expected")
+        if error is not None and not (torch.is_tensor(error) and error.device == self.device and error.dtype == torch.float64 and error.numel() == 1):
+            raise L.VtError(f"StepGuard.close: error is a float64 scalar on {self.device}")
+        lib = L.lib()
+        with torch.cuda.device(self.device):
+            grads = [g.detach().reshape(-1) for g in grads]
+            stream, args = L.stream_ptr(), []
+            for g, seg, out, ws in zip(grads, self._seg, self._out, self._ws):
+                grad_stats(g, seg, ws=ws, out=out)
+                args += [out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), seg.shape[0]]
+            args += [None, None, None, 0] * (3 - len(grads))
+            L.check(lib.vt_grad_guard_close(*args, L.dptr(error.detach().reshape(1)) if error is not None else None,
+                                            self.max_norm if self.max_norm is not None else 0.0, self.record.data_ptr(), self.ring, stream))
+            if self.max_norm is not None:
+                for g in grads:
+                    L.check(lib.vt_grad_scale(L.dptr(g), g.numel(), self.coef.data_ptr(), self.skip.data_ptr(), stream))
+        return self.skip
+
+    def _slot_dict(self, raw, at):
+        S = self.n_seg
+        head = raw[at:at + _GUARD_SLOT_HEAD]
+        body = raw[at + _GUARD_SLOT_HEAD:at + self._slot]
+        sumsq, maxabs, nonfinite = body[:8 * S].view(np.float64), body[8 * S:12 * S].view(np.float32), body[12 * S:16 * S].view(np.int32)
+        return {"step": int(head[24:32].view(np.int64)[0]), "norm": float(head[0:8].view(np.float64)[0]), "error": float(head[8:16].view(np.float64)[0]),
+                "coef": float(head[16:20].view(np.float32)[0]), "skip": bool(head[20:24].view(np.int32)[0]),
+                "sumsq": {k: float(v) for k, v in zip(self.names, sumsq)}, "maxabs": {k: float(v) for k, v in zip(self.names, maxabs)},
+                "nonfinite": {k: int(v) for k, v in zip(self.names, nonfinite)}}
+
+    def read(self):
+        """the record as a host dict, in ONE copy (it waits for the stream): ``steps`` and ``skipped`` (counters since the guard was built); of the last step
+        ``step`` (its index), ``norm``, ``coef``, ``skip``, ``error`` and per name ``sumsq``, ``maxabs``, ``nonfinite``; ``ring``: the same dicts for the last
+        ``record`` steps, oldest first.  Before the first ``close`` the last step is all zeros and the ring empty."""
+        raw = self.record.cpu().numpy().view(np.uint8)
+        steps, skipped = (int(x) for x in raw[:_GUARD_HEAD].view(np.int64))
+        out = {"steps": steps, "skipped": skipped}
+        out.update(self._slot_dict(raw, _GUARD_HEAD))
+        out["ring"] = [self._slot_dict(raw, _GUARD_HEAD + (1 + t % self.ring) * self._slot) for t in range(max(0, steps - self.ring), steps)] if self.ring else []
+        return out

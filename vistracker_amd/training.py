@@ -205,14 +205,21 @@ class SIFNetTrainer:
                 error, losses_all = tr.train_step(batch, images, cc)
         net = tr.export(images)                     # a SIFNetQuery with the trained decoders and a SIFNetEncoder of the trained encoders, maps of `images` set
 
+    ``guard=True`` puts an ``ops.StepGuard`` (``.guard``) between the gradient mean and the optimiser steps: a step whose gradients or objective hold a NaN or Inf
+    is skipped on the device, on every rank alike, and ``guard.read()`` (for epoch boundaries, as ``in_sync()``) tells which tensor blew up and what the norms
+    were; ``clip_norm`` clips the global gradient norm as ``clip_grad_norm_`` does; ``record`` = K keeps the last K steps.  Without it every method does what
+    it did before, launch for launch.
+
     ``sd`` carries the reference's keys (a leading ``module.`` is stripped).  Only the shared triplane encoder is served: per-view encoders
     (``triplane_encoder_0.`` ...) raise.  The query needs as many triplane stacks as image stacks (chore_triplane.py:146-147 indexes both with one counter)."""
 
     def __init__(self, sd, camera=None, num_stack=3, num_hourglass=2, triplane_stack=3, lr=1e-3, milestones=(), gamma=0.3, max_dist=5.0,
-                 loss_weights=ops.LOSS_WEIGHTS, device="cuda:0", group=None):
+                 loss_weights=ops.LOSS_WEIGHTS, device="cuda:0", group=None, guard=False, clip_norm=None, record=0):
         from .encoder import EncoderAdam, TrainableHGFilter, state_dict_under
         from .sifnet import SIFNetQuery
         sd = state_dict_under(sd, "")
+        if not guard and (clip_norm is not None or record):
+            raise L.VtError("SIFNetTrainer: clip_norm and record belong to the step guard; pass guard=True with them")
         if any(k.startswith("triplane_encoder_") for k in sd):
             raise L.VtError("SIFNetTrainer: this checkpoint holds per-view triplane encoders (triplane_encoder_0. ...); only the shared form "
                             "(triplane_encoder.) is trained here")
@@ -233,6 +240,7 @@ class SIFNetTrainer:
         # the three flat gradient buffers of the network (the decoders' is the one autograd makes anew every step: handed to the reducer per call)
         self.reducer = ops.RankMean([self.image_optimizer.grad, self.tri_optimizer.grad, self.params.flat.detach()], group)
         self.group = self.reducer.group
+        self.guard = self._make_guard(clip_norm, record) if guard else None
         if self.group is not None and not self.in_sync():
             raise L.VtError(f"SIFNetTrainer: rank {self.reducer.rank} of {self.reducer.world} was built from weights that differ from another rank's; "
                             "data-parallel steps need the same parameters and moments on every rank")
@@ -283,9 +291,42 @@ class SIFNetTrainer:
         error.backward()
         return error.detach(), losses_all
 
-    def apply(self):
-        """the three optimiser steps on whatever the gradient buffers hold"""
-        self.image_optimizer.step(); self.tri_optimizer.step(); self.optimizer.step()
+    def _make_guard(self, clip_norm, record):
+        """the ``ops.StepGuard`` over the three flat gradient buffers: every stepped leaf of the two encoders at its ``EncoderAdam`` offset (the 64-float padding
+        belongs to no segment), the decoders' 40 tensors at their ``vt_decoder_param_offset`` offsets, named by the reference's checkpoint keys in the order of
+        ``state_dict()``"""
+        segments, names = [], []
+        for prefix, enc, opt in ((IMAGE_PREFIX, self.image, self.image_optimizer), (TRIPLANE_PREFIX, self.tri, self.tri_optimizer)):
+            key = {id(p): k for k, p in reversed(enc.named_parameters())}
+            segments.append([(o, p.numel()) for p, o in zip(opt.params, opt._offs)])
+            names.append([prefix + key[id(p)] for p in opt.params])
+        lib, segs, ns = L.lib(), [], []
+        for h, head in enumerate(ops.HEADS):
+            for l, i in enumerate(ops.STATE_DICT_LAYERS):
+                for is_bias, kind in enumerate(("weight", "bias")):
+                    segs.append((int(lib.vt_decoder_param_offset(h, l, is_bias)), self.params.views[(head, l, kind)].numel()))
+                    ns.append(f"{ops.STATE_DICT_MODULES[head]}.{i}.{kind}")
+        return ops.StepGuard([self.image_optimizer.grad, self.tri_optimizer.grad, self.params.flat.detach()], segments + [segs], names + [ns],
+                             max_norm=clip_norm, record=record)
+
+    def _guard_error(self, error):
+        """the objective the guard looks at.  Every rank must take the same decision or the ranks part for good, and the objective is the one input of the
+        decision that differs between them: with a group and the guard on, the ranks' values are gathered (8 bytes each) and added in rank order, which is also
+        the sum a single rank forms over as many micro-batches.  Without a guard or a group: ``error`` as it is, no collective."""
+        if self.guard is None or self.group is None:
+            return error
+        return self.reducer.gather(error.detach().reshape(1)).sum()
+
+    def apply(self, error=None):
+        """the three optimiser steps on whatever the gradient buffers hold.  With the guard on, ``guard.close`` first measures the three buffers, decides on the
+        device whether the step is skipped (a NaN or Inf in a gradient, or in ``error``, the step's objective as a float64 device scalar) and clips them to
+        ``clip_norm``; the three steps then take that decision as their stop flag.  A skipped step leaves every parameter and moment untouched; the optimisers'
+        ``t`` advances all the same."""
+        if self.guard is None:
+            self.image_optimizer.step(); self.tri_optimizer.step(); self.optimizer.step()
+            return
+        skip = self.guard.close(self.flat_grads(), error)
+        self.image_optimizer.step(skip=skip); self.tri_optimizer.step(skip=skip); self.optimizer.step(skip=skip)
 
     def flat_grads(self):
         """the three flat gradient buffers after a ``backward``: image encoder, triplane encoder, decoders.  An encoder leaf whose ``.grad`` autograd replaced is
@@ -302,7 +343,7 @@ class SIFNetTrainer:
         error, losses_all = self.backward(batch, images, crop_center)
         if self.group is not None:
             self.reducer.reduce(self.flat_grads())
-        self.apply()
+        self.apply(self._guard_error(error))
         return error, losses_all
 
     def train_step_micro(self, micro_batches):
@@ -326,7 +367,7 @@ class SIFNetTrainer:
         grads = self.reducer.reduce_local(rows, self.flat_grads())
         if self.group is not None:
             self.reducer.reduce(grads)
-        self.apply()
+        self.apply(self._guard_error(torch.stack(errors).sum()) if self.guard is not None else None)          # the sum of the micro errors: for finiteness and the record only
         return torch.stack(errors), torch.stack(losses)
 
     def in_sync(self):
