@@ -963,6 +963,36 @@ int vt_grad_guard_close(const double *sumsq0, const float *maxabs0, const int *n
                         const double *error, double max_norm, void *record, int ring, void *stream);
 int vt_grad_scale(float *g, long n, const float *coef, const int *skip, void *stream);
 
+/* ---- HVOP-Net training, first block (formertrain.hip): one pre-norm transformer encoder layer with a taped forward and a hand-written backward, and the final
+ * LayerNorm of a TransformerV2.  fp32 row-major tensors; x, y, d_y, d_x are (B, T, D); pos (T, D); key_padding_mask (B, T) bytes, 1 = key ignored, NULL = none.
+ * `params`: a HOST array of twelve device pointers in the reference's layouts and this order: self_attn.in_proj_weight (3D, D), self_attn.in_proj_bias,
+ * self_attn.out_proj.weight, self_attn.out_proj.bias, linear1.weight (F, D), linear1.bias, linear2.weight (D, F), linear2.bias, norm1.weight, norm1.bias,
+ * norm2.weight, norm2.bias.  activation: 0 relu, 1 gelu (exact erf), 2 leaky_relu 0.01.  Dropout p in [0, 1) with a 64-bit seed: keep-masks from
+ * csrc/dropout_hash.h at the four sites named there; p = 0 hashes nothing and is the identity.
+ * SHAPES: 1 <= T <= 192, D % 16 == 0 <= 160, F % 16 == 0 <= 256, D / H in {16, 32, 160}; anything else is VT_ERR_ARG and launches nothing (the size queries
+ * return -1).  ARITHMETIC: exact fp32 products on v_mfma_f32_16x16x4_f32, LayerNorm statistics and backward sums in fp64, sums over the B T rows in chunks of 512
+ * rows added in fp64 in chunk order; no atomics, the same bits on every call, a power-of-two scale of d_y scales every result bit for bit; with p = 0 a clip's y
+ * and d_x rows do not depend on the other clips.  A clip whose keys are all masked is outside the contract (memory-safe, value undefined).  Pointers 8-byte aligned.
+ *
+ * vt_former_layer_forward (TransformerEncoderLayer.forward_pre, former_deci.py:77-93): y = y1 + drop2(linear2(drop(act(linear1(LN2(y1)))))),
+ *   y1 = x + drop1(self_attn(LN1(x) + pos, LN1(x) + pos, LN1(x))).  tape: vt_former_layer_tape_floats floats (layout in formertrain.hip), or NULL for the
+ *   inference-only forward, which needs `workspace` of 4 B T D floats instead (NULL otherwise).
+ * vt_former_layer_backward (the autograd backward of the same lines): d_x and `d_params`, a HOST array of twelve device pointers in the order of `params` (or NULL);
+ *   a NULL pointer skips that output, accumulate != 0 adds onto every output.  workspace: vt_former_layer_workspace_floats floats, nothing to initialise.
+ * vt_layernorm_forward / vt_layernorm_backward (encoder.norm of TransformerEncoder, former_deci.py:64-65): x, y (M, D); stats (M, 2) fp64 {mean, rstd}, NULL in
+ *   the forward to skip them; d_x / d_weight / d_bias may be NULL; workspace: vt_layernorm_backward_workspace_floats(M, D) floats. */
+long vt_former_layer_tape_floats(int B, int T, int D, int H, int F);
+long vt_former_layer_workspace_floats(int B, int T, int D, int H, int F);
+int vt_former_layer_forward(const float *x, const float *pos, const unsigned char *key_padding_mask, const float *const *params, int B, int T, int D, int H,
+                            int F, int activation, float p, unsigned long long seed, float *y, float *tape, float *workspace, void *stream);
+int vt_former_layer_backward(const float *d_y, const float *tape, const float *x, const float *pos, const unsigned char *key_padding_mask,
+                             const float *const *params, int B, int T, int D, int H, int F, int activation, float p, unsigned long long seed,
+                             float *d_x, float *const *d_params, int accumulate, float *workspace, void *stream);
+long vt_layernorm_backward_workspace_floats(long M, int D);
+int vt_layernorm_forward(const float *x, const float *weight, const float *bias, long M, int D, float *y, double *stats, void *stream);
+int vt_layernorm_backward(const float *d_y, const float *x, const double *stats, const float *weight, long M, int D, float *d_x, float *d_weight,
+                          float *d_bias, int accumulate, float *workspace, void *stream);
+
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two
  * workgroups of 256 threads per CU, non-trivial operands), out[1] = shader clock sustained during it (MHz: s_memtime against the 100 MHz s_memrealtime),

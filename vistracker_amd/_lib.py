@@ -211,6 +211,14 @@ SIGNATURES = {
     "vt_grad_scale": (ci, [fp, cl, fp, fp, vp]),                                      # g, n, coef, skip | stream
     "vt_calibrate_workspace_bytes": (cl, []),
     "vt_calibrate": (ci, [vp, C.POINTER(C.c_double), vp]),
+    # csrc/formertrain.hip: x, pos, mask, params[12] | B, T, D, H, F, activation, p, seed | y, tape, workspace, stream
+    "vt_former_layer_tape_floats": (cl, [ci, ci, ci, ci, ci]),
+    "vt_former_layer_workspace_floats": (cl, [ci, ci, ci, ci, ci]),
+    "vt_former_layer_forward": (ci, [fp, fp, fp, vp, ci, ci, ci, ci, ci, ci, cf, C.c_ulonglong, fp, fp, fp, vp]),
+    "vt_former_layer_backward": (ci, [fp, fp, fp, fp, fp, vp, ci, ci, ci, ci, ci, ci, cf, C.c_ulonglong, fp, vp, ci, fp, vp]),
+    "vt_layernorm_backward_workspace_floats": (cl, [cl, ci]),
+    "vt_layernorm_forward": (ci, [fp, fp, fp, cl, ci, fp, fp, vp]),
+    "vt_layernorm_backward": (ci, [fp, fp, fp, fp, cl, ci, fp, fp, fp, ci, fp, vp]),
 }
 
 _lib = None

@@ -1,0 +1,192 @@
+"""HVOP-Net training, first block: the encoders of ``infill.ConditionalMInfiller`` with gradients.  Mirror of
+
+    model.transformers.former_deci.TransformerV2 / TransformerEncoderLayer.forward_pre          (former_deci.py:33-175; kernels: csrc/formertrain.hip)
+    model.infill.mfiller_cond.ConditionalMInfiller.forward                                       (mfiller_cond.py:84-107)
+    trainer.trainer_infiller.TrainerInfiller.motion_losses / trainer_cinfiller.compute_loss      (trainer_infiller.py:33-47, trainer_cinfiller.py:30-44)
+
+The encoder layers run ``ops.former_layer_train`` (a taped HIP forward and a hand-written HIP backward per layer); the two input projections and the predictor MLP
+are six small GEMMs left to torch autograd.  Dropout masks come from the counter-based hash of csrc/dropout_hash.h, restated here for the per-layer seeds: a step
+is a function of its ``seed``.  ``infill.py`` (inference) is untouched; ``export()`` hands the trained weights to it."""
+from __future__ import annotations
+
+import torch
+import torch.nn.functional as F
+
+from . import _lib as L
+from . import infill, ops
+from .training import multistep_lr
+
+_M32 = 0xffffffff
+
+
+def _mix32(x):
+    x ^= x >> 16; x = (x * 0x7feb352d) & _M32; x ^= x >> 15; x = (x * 0x846ca68b) & _M32; x ^= x >> 16
+    return x
+
+
+def dropout_hash(seed: int, site: int, index: int) -> int:
+    """csrc/dropout_hash.h on python integers"""
+    h = _mix32((seed & _M32) ^ ((0x9e3779b9 * (site + 1)) & _M32))
+    h = _mix32(h ^ ((seed >> 32) & _M32))
+    h = _mix32(h ^ (index & _M32))
+    return _mix32(h ^ ((index >> 32) & _M32))
+
+
+def layer_seed(seed: int, encoder_id: int, layer: int) -> int:
+    """the 64-bit seed of layer ``layer`` of encoder ``encoder_id``: two hashes of (seed, site 100 + encoder_id, 2 layer | 2 layer + 1)"""
+    return dropout_hash(seed, 100 + encoder_id, 2 * layer) | (dropout_hash(seed, 100 + encoder_id, 2 * layer + 1) << 32)
+
+
+def _leaf(t, device):
+    t = t if torch.is_tensor(t) else torch.as_tensor(__import__("numpy").asarray(t))
+    return t.detach().to(device=device, dtype=torch.float32).contiguous().clone().requires_grad_(True)
+
+
+class TrainableTransformerV2:
+    """``TransformerV2`` with gradients: ``num_layers`` pre-norm layers (former_deci.py:143-147 always builds them pre-norm; ``pre_norm`` only decides whether the
+    final ``encoder.norm`` exists), the cached sine position table, parameters as leaves under the reference's state_dict keys."""
+
+    def __init__(self, params, num_layers, d_model, num_heads, activation, pre_norm, dropout=0.0, device="cuda:0", encoder_id=0):
+        self.L, self.D, self.H, self.activation, self.has_norm = int(num_layers), int(d_model), int(num_heads), activation, bool(pre_norm)
+        self.dropout, self.dev, self.encoder_id, self.training = float(dropout), torch.device(device), int(encoder_id), True
+        if activation not in ops.FORMER_ACT:
+            raise L.VtError(f"TrainableTransformerV2: activation {activation!r}; one of {sorted(ops.FORMER_ACT)}")
+        self.params = params
+        self._pos = {}
+
+    @classmethod
+    def from_state_dict(cls, sd, prefix, num_layers, d_model, num_heads, dim_feedforward, activation, pre_norm, dropout=0.0, device="cuda:0", encoder_id=0):
+        keys = [f"encoder.layers.{i}.{k}" for i in range(num_layers) for k in ops.FORMER_PARAM_KEYS] + (["encoder.norm.weight", "encoder.norm.bias"] if pre_norm else [])
+        params = {k: _leaf(sd[prefix + k], device) for k in keys}
+        F_ = params["encoder.layers.0.linear1.weight"].shape[0] if num_layers else dim_feedforward
+        if F_ != dim_feedforward:
+            raise L.VtError(f"TrainableTransformerV2: linear1 has {F_} rows, dim_feedforward is {dim_feedforward}")
+        return cls(params, num_layers, d_model, num_heads, activation, pre_norm, dropout, device, encoder_id)
+
+    def train(self):
+        self.training = True
+        return self
+
+    def eval(self):
+        self.training = False
+        return self
+
+    def named_parameters(self):
+        return list(self.params.items())
+
+    def state_dict(self):
+        return {k: v.detach().clone() for k, v in self.params.items()}
+
+    def pos(self, T):
+        if T not in self._pos:
+            self._pos[T] = infill.position_embedding_sine_1d(T, self.D // 2, self.D).to(self.dev).contiguous()
+        return self._pos[T]
+
+    def __call__(self, x, key_padding_mask=None, seed=None):
+        p = self.dropout if self.training else 0.0
+        if p > 0 and seed is None:
+            raise L.VtError("TrainableTransformerV2: a training forward with dropout needs a seed")
+        pos = self.pos(x.shape[1])
+        for l in range(self.L):
+            ps = [self.params[f"encoder.layers.{l}.{k}"] for k in ops.FORMER_PARAM_KEYS]
+            x = ops.former_layer_train(x, pos, key_padding_mask, ps, self.H, self.activation, p, layer_seed(seed, self.encoder_id, l) if p > 0 else 0)
+        if self.has_norm:
+            x = ops.layernorm_train(x, self.params["encoder.norm.weight"], self.params["encoder.norm.bias"])
+        return x
+
+
+class TrainableConditionalMInfiller:
+    """``ConditionalMInfiller`` (mfiller_cond.py:84-107) that trains; ``opt``: the namespace of config/cmf-k4-lrot.json.  Encoder ids: 0 SMPL, 1 object, 2 joint."""
+
+    ENCODERS = (("encoder_smpl.", "smpl"), ("encoder_obj.", "obj"), ("encoder_joint.", "joint"))
+
+    def __init__(self, sd, opt, dropout=None, device="cuda:0"):
+        sd = infill._strip(sd); self.opt, self.dev = opt, torch.device(device)
+        self.sd_keys = list(sd)
+        dj = opt.d_model_smpl + opt.d_model_obj
+        self.enc = {}
+        for e, (prefix, tag) in enumerate(self.ENCODERS):
+            d = dj if tag == "joint" else getattr(opt, f"d_model_{tag}")
+            self.enc[tag] = TrainableTransformerV2.from_state_dict(
+                sd, prefix, getattr(opt, f"num_layers_{tag}"), d, getattr(opt, f"num_heads_{tag}"), getattr(opt, f"dim_forward_{tag}"),
+                getattr(opt, f"activation_{tag}"), getattr(opt, f"pre_norm_{tag}"), getattr(opt, f"dropout_{tag}") if dropout is None else dropout, self.dev, e)
+        self.plain = {k: _leaf(sd[k], self.dev) for k in sd if not k.startswith(tuple(p for p, _ in self.ENCODERS))}
+        self.n_head = len(opt.hidden_dims) + 1
+
+    @classmethod
+    def from_state_dict(cls, sd, opt, dropout=None, device="cuda:0"):
+        return cls(sd, opt, dropout, device)
+
+    def train(self):
+        for e in self.enc.values():
+            e.train()
+        return self
+
+    def eval(self):
+        for e in self.enc.values():
+            e.eval()
+        return self
+
+    def named_parameters(self):
+        out = dict(self.plain)
+        for (prefix, tag) in self.ENCODERS:
+            out.update({prefix + k: v for k, v in self.enc[tag].params.items()})
+        return [(k, out[k]) for k in self.sd_keys if k in out]
+
+    def state_dict(self):
+        return {k: v.detach().clone() for k, v in self.named_parameters()}
+
+    def export(self):
+        return infill.ConditionalMInfiller(self.state_dict(), self.opt, device=self.dev)
+
+    def __call__(self, data_smpl, mask_smpl, data_obj, mask_obj, seed=None):
+        P = self.plain
+        fs = self.enc["smpl"](F.linear(data_smpl.to(self.dev).float(), P["feat_proj_smpl.weight"], P["feat_proj_smpl.bias"]), mask_smpl.to(self.dev), seed)
+        fo = self.enc["obj"](F.linear(data_obj.to(self.dev).float(), P["feat_proj_obj.weight"], P["feat_proj_obj.bias"]), mask_obj.to(self.dev), seed)
+        x = self.enc["joint"](torch.cat([fs, fo], -1).contiguous(), None, seed)
+        for i in range(self.n_head):
+            x = F.linear(x, P[f"predictor.{2 * i}.weight"], P[f"predictor.{2 * i}.bias"])
+            if i + 1 < self.n_head:
+                x = F.leaky_relu(x)
+        return x
+
+
+def motion_losses(gt, pred, lw_pose=1.0, lw_accel=0.1):
+    """(loss_accel, loss_pos) of trainer_infiller.py:33-47: the L1 mean times lw_pose, the L1 mean of the second differences along T times lw_accel"""
+    loss_pos = F.l1_loss(pred, gt, reduction="mean") * lw_pose
+    acc = lambda a: a[:, :-2] - 2 * a[:, 1:-1] + a[:, 2:]
+    loss_accel = F.l1_loss(acc(pred), acc(gt), reduction="mean") * lw_accel
+    return loss_accel, loss_pos
+
+
+class HVOPTrainer:
+    """one training step of HVOP-Net (trainer_cinfiller.py:30-44 + the Adam / MultiStepLR of the reference's base trainer): zero grads, forward, ``motion_losses``,
+    one ``backward()``, one ``ops.FusedAdam.step()`` over the leaves.  Nothing in ``train_step`` waits on the host."""
+
+    def __init__(self, sd, opt, lr=1e-4, milestones=(30, 40), gamma=0.1, dropout=None, lw_pose=1.0, lw_accel=0.1, device="cuda:0"):
+        self.model = TrainableConditionalMInfiller(sd, opt, dropout, device).train()
+        self.names = [k for k, _ in self.model.named_parameters()]
+        self.optimizer = ops.FusedAdam([p for _, p in self.model.named_parameters()], lr=lr)
+        self.lr0, self.milestones, self.gamma, self.lw = float(lr), tuple(milestones), float(gamma), (float(lw_pose), float(lw_accel))
+
+    def set_step(self, epoch):
+        lr = multistep_lr(self.lr0, self.milestones, self.gamma, epoch)
+        self.optimizer.lrs = [lr] * len(self.optimizer.lrs)
+        return lr
+
+    def train_step(self, batch, seed=0):
+        """-> (loss (), sep_loss (2,) = [loss_pos, loss_accel]) device tensors of the objective BEFORE the update"""
+        dev = self.model.dev
+        self.optimizer.zero_grad()
+        pred = self.model(batch["data_smpl"], batch["mask_smpl"], batch["data_obj"], batch["mask_obj"], seed)
+        loss_accel, loss_pos = motion_losses(batch["gt_obj"].to(dev).float(), pred, *self.lw)
+        loss = loss_pos + loss_accel
+        loss.backward()
+        self.optimizer.step()
+        return loss.detach(), torch.stack([loss_pos.detach(), loss_accel.detach()])
+
+    def state_dict(self):
+        return self.model.state_dict()
+
+    def export(self):
+        return self.model.export()

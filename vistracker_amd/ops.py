@@ -1657,3 +1657,150 @@ class StepGuard:
         out.update(self._slot_dict(raw, _GUARD_HEAD))
         out["ring"] = [self._slot_dict(raw, _GUARD_HEAD + (1 + t % self.ring) * self._slot) for t in range(max(0, steps - self.ring), steps)] if self.ring else []
         return out
+
+
+# ---- HVOP-Net training (csrc/formertrain.hip): one pre-norm encoder layer and the final LayerNorm of a TransformerV2 as autograd Functions ----------------
+FORMER_PARAM_KEYS = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias", "linear1.weight", "linear1.bias",
+                     "linear2.weight", "linear2.bias", "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias")
+FORMER_ACT = {"relu": 0, "gelu": 1, "leaky_relu": 2}
+
+
+def _former_ptrs(ts):
+    return (C.c_void_p * 12)(*[None if t is None else L.dptr(t) for t in ts])
+
+
+def former_tape_views(tape, B, T, D, H, F):
+    """the named tensors of a layer tape (layout: csrc/formertrain.hip): fp64 mean1, rstd1, mean2, rstd2 (B, T, 1); fp32 qkv (B, T, 3D), O, y1 (B, T, D), h (B, T, F),
+    lse (B, H, T)"""
+    M = B * T
+    st = tape[:8 * M].view(torch.float64).view(2, M, 2)
+    out = {"mean1": st[0, :, 0].reshape(B, T, 1), "rstd1": st[0, :, 1].reshape(B, T, 1), "mean2": st[1, :, 0].reshape(B, T, 1), "rstd2": st[1, :, 1].reshape(B, T, 1)}
+    o = 8 * M
+    for k, n, shape in (("qkv", 3 * M * D, (B, T, 3 * D)), ("O", M * D, (B, T, D)), ("y1", M * D, (B, T, D)), ("h", M * F, (B, T, F)), ("lse", B * H * T, (B, H, T))):
+        out[k] = tape[o:o + n].view(shape); o += n
+    return out
+
+
+def _former_check(x, pos, key_padding_mask, params, H, activation, extra=()):
+    """float32 contiguous device tensors of the shapes the kernels assume: they read raw pointers"""
+    f32 = lambda t: torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32           # noqa: E731
+    if not f32(x) or x.dim() != 3:
+        raise L.VtError("former layer: x must be a float32 device tensor (B, T, D)")
+    B, T, D = x.shape
+    if activation not in FORMER_ACT:
+        raise L.VtError(f"former layer: activation {activation!r}; one of {sorted(FORMER_ACT)}")
+    if not f32(pos) or tuple(pos.shape) != (T, D):
+        raise L.VtError(f"former layer: pos must be float32 ({T}, {D})")
+    if len(params) != 12 or not all(f32(q) for q in params) or params[4].dim() != 2:
+        raise L.VtError("former layer: twelve float32 device parameters in FORMER_PARAM_KEYS order expected")
+    F = params[4].shape[0]
+    shapes = ((3 * D, D), (3 * D,), (D, D), (D,), (F, D), (F,), (D, F), (D,), (D,), (D,), (D,), (D,))
+    for k, q, s in zip(FORMER_PARAM_KEYS, params, shapes):
+        if tuple(q.shape) != s:
+            raise L.VtError(f"former layer: {k} has shape {tuple(q.shape)}, expected {s}")
+    if key_padding_mask is not None and (not torch.is_tensor(key_padding_mask) or tuple(key_padding_mask.shape) != (B, T)
+                                         or key_padding_mask.dtype not in (torch.bool, torch.uint8)):
+        raise L.VtError(f"former layer: key_padding_mask must be bool / uint8 ({B}, {T})")
+    for name, t, s in extra:
+        if t is not None and (not f32(t) or tuple(t.shape) != tuple(s)):
+            raise L.VtError(f"former layer: {name} must be float32 {tuple(s)}")
+    return B, T, D, F
+
+
+def former_layer_forward(x, pos, key_padding_mask, params, H, activation, p=0.0, seed=0, tape=True):
+    """vt_former_layer_forward -> (y, tape or None).  ``params``: the twelve tensors in FORMER_PARAM_KEYS order; ``key_padding_mask`` (B, T) uint8 / bool or None."""
+    B, T, D, F = _former_check(x, pos, key_padding_mask, params, H, activation)
+    lib = L.lib()
+    n = int(lib.vt_former_layer_tape_floats(B, T, D, H, F))
+    if n < 0:
+        raise L.VtError(f"former layer: unsupported shape B {B} T {T} D {D} H {H} F {F} (T <= 192, D % 16 == 0 <= 160, F % 16 == 0 <= 256, D / H in {{16, 32, 160}})")
+    y = torch.empty_like(x)
+    tp = torch.empty(n, dtype=torch.float32, device=x.device) if tape else None
+    ws = None if tape else torch.empty(4 * B * T * D, dtype=torch.float32, device=x.device)
+    m = None if key_padding_mask is None else key_padding_mask.to(torch.uint8).contiguous()
+    L.check(lib.vt_former_layer_forward(L.dptr(x), L.dptr(pos), L.dptr(m), _former_ptrs(params), B, T, D, H, F, FORMER_ACT[activation], float(p), int(seed),
+                                        L.dptr(y), L.dptr(tp), L.dptr(ws), L.stream_ptr()))
+    return y, tp
+
+
+def former_layer_backward(d_y, tape, x, pos, key_padding_mask, params, H, activation, p=0.0, seed=0, want_dx=True, want=None, out=None, accumulate=False):
+    """vt_former_layer_backward -> (d_x or None, [twelve gradients or None]).  ``want``: twelve flags (default all); ``out``: (d_x, [twelve]) buffers to write / add into."""
+    B, T, D, F = _former_check(x, pos, key_padding_mask, params, H, activation, extra=(("d_y", d_y, x.shape),))
+    lib = L.lib()
+    n = int(lib.vt_former_layer_workspace_floats(B, T, D, H, F))
+    nt = int(lib.vt_former_layer_tape_floats(B, T, D, H, F))
+    if n < 0 or nt < 0:
+        raise L.VtError(f"former layer: unsupported shape B {B} T {T} D {D} H {H} F {F}")
+    if not (torch.is_tensor(tape) and tape.is_cuda and tape.dtype == torch.float32 and tape.numel() == nt):
+        raise L.VtError(f"former layer: the tape must be the float32 tensor of {nt} values a taped forward of this shape returned")
+    if out is not None:
+        _former_check(x, pos, key_padding_mask, params, H, activation, extra=[("d_x", out[0], x.shape)] + [(k, t, q.shape) for k, t, q in zip(FORMER_PARAM_KEYS, out[1], params)])
+    ws = torch.empty(n, dtype=torch.float32, device=x.device)
+    want = [True] * 12 if want is None else list(want)
+    if out is not None:
+        d_x, grads = out
+    else:
+        d_x = torch.empty_like(x) if want_dx else None
+        grads = [torch.empty_like(q) if w else None for q, w in zip(params, want)]
+    m = None if key_padding_mask is None else key_padding_mask.to(torch.uint8).contiguous()
+    L.check(lib.vt_former_layer_backward(L.dptr(d_y), L.dptr(tape), L.dptr(x), L.dptr(pos), L.dptr(m), _former_ptrs(params), B, T, D, H, F, FORMER_ACT[activation],
+                                         float(p), int(seed), L.dptr(d_x), _former_ptrs(grads), int(bool(accumulate)), L.dptr(ws), L.stream_ptr()))
+    return d_x, grads
+
+
+class _FormerLayerFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, pos, mask, H, activation, p, seed, *params):
+        x = x.contiguous(); params = [q.contiguous() for q in params]
+        y, tape = former_layer_forward(x, pos, mask, params, H, activation, p, seed)
+        ctx.save_for_backward(x, pos, tape, *params)
+        ctx.mask, ctx.cfg = mask, (H, activation, p, seed)
+        return y
+
+    @staticmethod
+    def backward(ctx, d_y):
+        x, pos, tape, *params = ctx.saved_tensors
+        H, activation, p, seed = ctx.cfg
+        want = list(ctx.needs_input_grad[7:])
+        d_x, grads = former_layer_backward(d_y.contiguous(), tape, x, pos, ctx.mask, params, H, activation, p, seed, want_dx=ctx.needs_input_grad[0], want=want)
+        return (d_x, None, None, None, None, None, None, *grads)
+
+
+def former_layer_train(x, pos, key_padding_mask, params, H, activation, p=0.0, seed=0):
+    """one pre-norm encoder layer (former_deci.py:77-93) under autograd: x (B, T, D) and the twelve ``params`` (FORMER_PARAM_KEYS order) receive gradients from the
+    hand-written backward.  No host wait in either direction."""
+    return _FormerLayerFn.apply(x, pos, key_padding_mask, H, activation, float(p), int(seed), *params)
+
+
+class _LayerNormFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        D = x.shape[-1]
+        if any(not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32) for t in (x, weight, bias)) or tuple(weight.shape) != (D,) or tuple(bias.shape) != (D,):
+            raise L.VtError(f"layernorm_train: float32 device tensors expected, weight and bias of shape ({D},)")
+        x = x.contiguous()
+        M = x.numel() // D
+        if L.lib().vt_layernorm_backward_workspace_floats(M, D) < 0:
+            raise L.VtError(f"layernorm_train: unsupported M {M} D {D} (D % 16 == 0, 16 <= D <= 160)")
+        y = torch.empty_like(x); stats = torch.empty(M, 2, dtype=torch.float64, device=x.device)
+        L.check(L.lib().vt_layernorm_forward(L.dptr(x), L.dptr(weight.contiguous()), L.dptr(bias.contiguous()), M, D, L.dptr(y), L.dptr(stats), L.stream_ptr()))
+        ctx.save_for_backward(x, weight, stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, d_y):
+        x, weight, stats = ctx.saved_tensors
+        D = x.shape[-1]; M = x.numel() // D
+        lib = L.lib()
+        ws = torch.empty(int(lib.vt_layernorm_backward_workspace_floats(M, D)), dtype=torch.float32, device=x.device)
+        d_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dw = torch.empty_like(weight) if ctx.needs_input_grad[1] else None
+        db = torch.empty_like(weight) if ctx.needs_input_grad[2] else None
+        L.check(lib.vt_layernorm_backward(L.dptr(d_y.contiguous()), L.dptr(x), L.dptr(stats), L.dptr(weight.contiguous()), M, D, L.dptr(d_x), L.dptr(dw), L.dptr(db), 0,
+                                          L.dptr(ws), L.stream_ptr()))
+        return d_x, dw, db
+
+
+def layernorm_train(x, weight, bias):
+    """nn.LayerNorm over the last dimension (eps 1e-5) under autograd: vt_layernorm_forward / vt_layernorm_backward"""
+    return _LayerNormFn.apply(x, weight, bias)
