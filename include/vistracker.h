@@ -993,6 +993,32 @@ int vt_layernorm_forward(const float *x, const float *weight, const float *bias,
 int vt_layernorm_backward(const float *d_y, const float *x, const double *stats, const float *weight, long M, int D, float *d_x, float *d_weight,
                           float *d_bias, int accumulate, float *workspace, void *stream);
 
+/* ---- HVOP-Net training, the data set (clipdata.hip): the decisions of a clip and the assembly of a batch of clips on the device.  The packed data of all
+ * sequences is fp32, concatenated over N frames: poses (N, 72) = columns [:69] + [111:114] of the SMPL-H pose (traindata_mfiller.py:102-105), trans, roots,
+ * obj_angles, obj_trans (N, 3); w2c_R (n_dates, 4, 3, 3) and w2c_t (n_dates, 4, 3) are KinectTransform's world2local_R / world2local_t per date and camera.
+ *
+ * vt_clip_draw replaces the np.random calls of TrainDataCMotionFiller.get_item and gen_masks (traindata_cmfiller.py:24-28, 46; traindata_mfiller.py:222-229) for
+ *   B clips, one thread a clip: kid in [0, 4) when multi_kinects, else 1; drop_len in [min_drop_len, max_drop_len]; start_fr in [start_fr_min,
+ *   min(T - drop_len, start_fr_max)); aug_start (B, aug_num) in [0, T - aug_num).  A decision is a function of (seed, epoch, clip_index[b], draw number) through
+ *   the hash and the sites of csrc/dropout_hash.h, mapped by multiply-shift: integers only, independent of the batch and of the launch.  A range that can be empty
+ *   (min(T - max_drop_len, start_fr_max) <= start_fr_min, T <= aug_num, max_drop_len < min_drop_len) is VT_ERR_ARG; nothing is clamped.  aug_num <= 64.
+ * vt_clip_build replaces get_smpl_input / get_obj_input (traindata_mfiller.py:231-296), the masking and the noise augmentation (traindata_cmfiller.py:34-51) and
+ *   utils/geometry_utils.py:63-77, 92-246, 284-354 under them.  start, date, kid, drop_len, start_fr (B,), aug_start (B, aug_num): clip b is frames
+ *   [start[b], start[b] + T) seen from camera kid[b] of date date[b].  Outputs: data_smpl, gt_smpl (B, T, 147) = 24 x 6D | translation; data_obj, gt_obj
+ *   (B, T, obj_dim), obj_dim 6 (6D) or 9 (6D | translation); mask_obj (B, T) bytes, 1 on [start_fr, start_fr + drop_len); mask_smpl all 0.  gt_* are taken
+ *   before masking; data_obj is multiplied by (1 - mask); with aug_num > 0 the aug_num windows of aug_num frames get 6D(axis(data_obj) + 0.5 z), the window with
+ *   the highest number winning an overlap and every window reading the masked, un-noised row.  z: `noise` (B, aug_num^2, 3), value (j aug_num + frame in window)
+ *   of window j, or with noise == NULL the Box-Muller normal of two hashed words (needs clip_index, seed, epoch as vt_clip_draw).  kid == 1 copies the
+ *   translations bit for bit.  fp32, one thread per rotation slot, no atomics, no workspace, the same bits on every call, clips independent of each other.
+ *   A clip whose start, kid or date lies outside its table reads nothing and comes out as zeros.  VT_ERR_ARG: a NULL pointer, obj_dim, aug_num, N < T. */
+int vt_clip_draw(const int *clip_index, int B, unsigned long long seed, unsigned int epoch, int T, int multi_kinects, int min_drop_len, int max_drop_len,
+                 int start_fr_min, int start_fr_max, int aug_num, int *kid, int *drop_len, int *start_fr, int *aug_start, void *stream);
+int vt_clip_build(const float *poses, const float *trans, const float *roots, const float *obj_angles, const float *obj_trans, long N,
+                  const float *w2c_R, const float *w2c_t, int n_dates, const int *start, const int *date, const int *kid, const int *drop_len,
+                  const int *start_fr, const int *aug_start, int B, int T, int obj_dim, int aug_num, const float *noise, const int *clip_index,
+                  unsigned long long seed, unsigned int epoch, float *data_smpl, float *data_obj, float *gt_smpl, float *gt_obj,
+                  unsigned char *mask_obj, unsigned char *mask_smpl, void *stream);
+
 /* ---- box calibration (measurement infrastructure of bench.py; no counterpart in the reference, which times whole processes: README.md:55) ------------------
  * Two fixed micro-kernels exercising the resources the dominant kernel of the fit is limited by: out[0] = dense f16 MFMA TFLOP/s (v_mfma_f32_16x16x32_f16, two
  * workgroups of 256 threads per CU, non-trivial operands), out[1] = shader clock sustained during it (MHz: s_memtime against the 100 MHz s_memrealtime),

@@ -9,7 +9,8 @@ import sys
 NO_SCRATCH = ("query_kernel<2, 2, true>", "query_kernel<2, 2, false>", "query_kernel<1, 3, true>", "query_kernel<1, 3, false>", "inp_panel_kernel", "ovl_panel_kernel",
               "ovl_score_kernel<true>", "ovl_score_kernel<false>", "pm_dist_kernel", "pm_vertex_kernel", "pm_setup_kernel", "ll_loss_kernel", "ll_finish_kernel",
               "dect::feat_kernel", "dect::mlp_kernel<0>", "dect::mlp_kernel<1>", "dect::wgrad_kernel", "dect::finish_kernel", "formt::k_ln_qkv", "formt::k_attn_fwd", "formt::k_out_ff", "formt::k_ff_bwd",
-              "formt::k_attn_bwd", "formt::k_qkv_bwd", "formt::k_wgrad", "formt::k_colsum", "formt::k_reduce", "formt::k_ln_fwd", "formt::k_ln_bwd")
+              "formt::k_attn_bwd", "formt::k_qkv_bwd", "formt::k_wgrad", "formt::k_colsum", "formt::k_reduce", "formt::k_ln_fwd", "formt::k_ln_bwd",
+              "clipd::draw_kernel", "clipd::build_kernel<6>", "clipd::build_kernel<9>")
 
 rows, cur = [], None
 for line in sys.stdin:

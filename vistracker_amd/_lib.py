@@ -219,6 +219,11 @@ SIGNATURES = {
     "vt_layernorm_backward_workspace_floats": (cl, [cl, ci]),
     "vt_layernorm_forward": (ci, [fp, fp, fp, cl, ci, fp, fp, vp]),
     "vt_layernorm_backward": (ci, [fp, fp, fp, fp, cl, ci, fp, fp, fp, ci, fp, vp]),
+    # csrc/clipdata.hip: clip_index, B | seed, epoch | T, multi_kinects, min_drop_len, max_drop_len, start_fr_min, start_fr_max, aug_num | kid, drop_len, start_fr, aug_start
+    "vt_clip_draw": (ci, [fp, ci, C.c_ulonglong, C.c_uint, ci, ci, ci, ci, ci, ci, ci, fp, fp, fp, fp, vp]),
+    # poses, trans, roots, obj_angles, obj_trans, N | w2c_R, w2c_t, n_dates | start, date, kid, drop_len, start_fr, aug_start | B, T, obj_dim, aug_num |
+    # noise, clip_index, seed, epoch | data_smpl, data_obj, gt_smpl, gt_obj, mask_obj, mask_smpl | stream
+    "vt_clip_build": (ci, [fp] * 5 + [cl] + [fp, fp, ci] + [fp] * 6 + [ci] * 4 + [fp, fp, C.c_ulonglong, C.c_uint] + [fp] * 6 + [vp]),
 }
 
 _lib = None

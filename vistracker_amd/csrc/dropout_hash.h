@@ -17,6 +17,16 @@
 #define VT_DROP_SITE_1 1u     /* dropout1 (attention branch), index (b T + t) D + c */
 #define VT_DROP_SITE_FF 2u    /* dropout (after the activation), index (b T + t) F + c */
 #define VT_DROP_SITE_2 3u     /* dropout2 (feed-forward branch), index (b T + t) D + c */
+/* the clip data set (clipdata.hip).  A clip's 64-bit key is hash(seed, KEY_LO, e) | hash(seed, KEY_HI, e) << 32 with e = epoch << 32 | global clip index; every
+ * decision of the clip is hash(key, site, draw number): a function of (seed, epoch, clip index, draw number) and of nothing else.  A draw h maps to [lo, hi) by
+ * multiply-shift, lo + ((uint64)h * (hi - lo) >> 32).  (Sites 100.. are the per-layer seeds of infill_training.layer_seed.) */
+#define VT_CLIP_SITE_KEY_LO 16u
+#define VT_CLIP_SITE_KEY_HI 17u
+#define VT_CLIP_SITE_KID 18u        /* draw 0: the camera, [0, 4) */
+#define VT_CLIP_SITE_DROP_LEN 19u   /* draw 0: [min_drop_len, max_drop_len + 1) */
+#define VT_CLIP_SITE_START_FR 20u   /* draw 0: [start_fr_min, min(T - drop_len, start_fr_max)) */
+#define VT_CLIP_SITE_AUG_START 21u  /* draw j < aug_num: the start of window j, [0, T - aug_num) */
+#define VT_CLIP_SITE_NOISE 22u      /* draws 2 v, 2 v + 1: the two words of the normal value v = (j aug_num + frame in window) 3 + component */
 
 VT_HASH_FN uint32_t vt_mix32(uint32_t x)
 {

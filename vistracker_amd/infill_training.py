@@ -185,8 +185,67 @@ class HVOPTrainer:
         self.optimizer.step()
         return loss.detach(), torch.stack([loss_pos.detach(), loss_accel.detach()])
 
+    def _loss(self, batch, seed=None):
+        pred = self.model(batch["data_smpl"], batch["mask_smpl"], batch["data_obj"], batch["mask_obj"], seed)
+        loss_accel, loss_pos = motion_losses(batch["gt_obj"].to(self.model.dev).float(), pred, *self.lw)
+        return loss_pos + loss_accel, torch.stack([loss_pos, loss_accel])
+
+    def train_epoch(self, data, epoch, seed, batch_size, world=1, rank=0):
+        """one epoch over ``data`` (``infill_data.HVOPClipData``): ``set_step(epoch)``, this rank's clip order from ``training.distributed_indices``, and per
+        batch of ``batch_size`` clips (a shorter tail is dropped, as the reference's loader drops it) one ``data.batch`` and one ``train_step`` whose dropout seed
+        is ``batch_seed(seed, epoch, batch number)``.  The order is checked and uploaded once, before the loop; nothing waits on the host.
+        -> (sum of the losses (), sum of [loss_pos, loss_accel] (2,), number of batches): device tensors and an int."""
+        from .training import distributed_indices
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise L.VtError(f"train_epoch: batch_size = {batch_size}")
+        self.set_step(epoch)
+        self.model.train()
+        order = distributed_indices(len(data), world, rank, epoch, seed)
+        n = len(order) // batch_size
+        dev = self.model.dev
+        total, sep = torch.zeros((), device=dev), torch.zeros(2, device=dev)
+        if n == 0:
+            return total, sep, 0
+        order = data._indices(order[:n * batch_size])
+        for i in range(n):
+            loss, s = self.train_step(data.batch(order[i * batch_size:(i + 1) * batch_size], seed, epoch), batch_seed(seed, epoch, i))
+            total += loss; sep += s
+        return total, sep, n
+
+    def validate(self, data, batch_size, max_batches=1024, seed=0):
+        """``compute_val_loss`` (trainer.py:321-346) with the infiller's cap of 1024 batches (trainer_infiller.py:55-57): eval mode, no gradients, a seeded shuffle
+        of the clips (the reference's is unseeded), the last short batch kept as its loader keeps it; the model is back in train mode afterwards.
+        -> (mean loss (), mean [loss_pos, loss_accel] (2,)) device tensors, the means over the batches; (inf, inf) without a batch."""
+        from .training import distributed_indices
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise L.VtError(f"validate: batch_size = {batch_size}")
+        order = distributed_indices(len(data), 1, 0, 0, seed, drop_last=False)
+        n = min(int(max_batches), -(-len(order) // batch_size))
+        dev = self.model.dev
+        total, sep = torch.zeros((), device=dev), torch.zeros(2, device=dev)
+        if n <= 0:
+            return total + float("inf"), sep + float("inf")
+        order = data._indices(order[:n * batch_size])
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                for i in range(n):
+                    loss, s = self._loss(data.batch(order[i * batch_size:(i + 1) * batch_size], seed, 0))
+                    total += loss; sep += s
+        finally:
+            self.model.train()
+        return total / n, sep / n
+
     def state_dict(self):
         return self.model.state_dict()
 
     def export(self):
         return self.model.export()
+
+
+def batch_seed(seed: int, epoch: int, batch: int) -> int:
+    """the 64-bit dropout seed of batch ``batch`` of epoch ``epoch``: two hashes of (seed, site 200 | 201, epoch << 32 | batch)"""
+    e = ((int(epoch) & _M32) << 32) | (int(batch) & _M32)
+    return dropout_hash(seed, 200, e) | (dropout_hash(seed, 201, e) << 32)

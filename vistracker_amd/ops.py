@@ -1804,3 +1804,104 @@ class _LayerNormFn(torch.autograd.Function):
 def layernorm_train(x, weight, bias):
     """nn.LayerNorm over the last dimension (eps 1e-5) under autograd: vt_layernorm_forward / vt_layernorm_backward"""
     return _LayerNormFn.apply(x, weight, bias)
+
+
+# --------------------------------------------------------------------------------------------------
+# HVOP-Net training: the clip data set (csrc/clipdata.hip)
+# --------------------------------------------------------------------------------------------------
+CLIP_DECISIONS = ("kid", "drop_len", "start_fr", "aug_start")
+CLIP_TABLES = (("poses", 72), ("trans", 3), ("roots", 3), ("obj_angles", 3), ("obj_trans", 3))
+
+
+def _clip_arg(what, t, dtype, shape, device=None):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise L.VtError(f"{what}: a device tensor is expected")
+    if device is not None and t.device != device:
+        raise L.VtError(f"{what}: on {t.device}, the other tensors are on {device}")
+    if t.dtype != dtype:
+        raise L.VtError(f"{what}: dtype {t.dtype}, {dtype} expected")
+    if tuple(t.shape) != tuple(shape):
+        raise L.VtError(f"{what}: shape {tuple(t.shape)}, {tuple(shape)} expected")
+    if not t.is_contiguous():
+        raise L.VtError(f"{what}: not contiguous")
+    return t
+
+
+def clip_draw(clip_index, seed, epoch, T, multi_kinects, min_drop_len, max_drop_len, start_fr_min, start_fr_max, aug_num):
+    """``vt_clip_draw``: the random decisions of TrainDataCMotionFiller.get_item / gen_masks for the clips ``clip_index`` (B,) int32 on the device (their GLOBAL
+    indices).  -> dict of int32 device tensors kid, drop_len, start_fr (B,), aug_start (B, aug_num): functions of (seed, epoch, clip index, draw number) alone.  A
+    range that can be empty raises; nothing is clamped."""
+    if not torch.is_tensor(clip_index) or clip_index.dim() != 1 or clip_index.numel() < 1:
+        raise L.VtError("clip_draw: clip_index is a (B,) int32 device tensor, B >= 1")
+    B, T, aug_num = clip_index.numel(), int(T), int(aug_num)
+    _clip_arg("clip_draw: clip_index", clip_index, torch.int32, (B,))
+    seed, epoch = int(seed), int(epoch)
+    if not (0 <= seed < 1 << 64 and 0 <= epoch < 1 << 32):
+        raise L.VtError(f"clip_draw: seed {seed} is a 64-bit, epoch {epoch} a 32-bit unsigned integer")
+    min_drop_len, max_drop_len, start_fr_min, start_fr_max = int(min_drop_len), int(max_drop_len), int(start_fr_min), int(start_fr_max)
+    if T < 1 or min_drop_len < 0 or max_drop_len < min_drop_len:
+        raise L.VtError(f"clip_draw: T = {T}, drop lengths [{min_drop_len}, {max_drop_len}]")
+    if start_fr_min < 0 or min(T - max_drop_len, start_fr_max) <= start_fr_min:
+        raise L.VtError(f"clip_draw: the start-frame range [{start_fr_min}, min({T} - {max_drop_len}, {start_fr_max})) is empty")
+    if not 0 <= aug_num <= 64 or (aug_num > 0 and T - aug_num <= 0):
+        raise L.VtError(f"clip_draw: aug_num = {aug_num} with T = {T}: the window-start range [0, T - aug_num) is empty, or aug_num is not in 0..64")
+    with torch.cuda.device(clip_index.device):
+        o = {k: torch.empty(B, dtype=torch.int32, device=clip_index.device) for k in CLIP_DECISIONS[:3]}
+        o["aug_start"] = torch.empty((B, aug_num), dtype=torch.int32, device=clip_index.device)
+        L.check(L.lib().vt_clip_draw(clip_index.data_ptr(), B, seed, epoch, T, 1 if multi_kinects else 0, min_drop_len, max_drop_len, start_fr_min, start_fr_max,
+                                     aug_num, o["kid"].data_ptr(), o["drop_len"].data_ptr(), o["start_fr"].data_ptr(),
+                                     o["aug_start"].data_ptr() if aug_num else None, L.stream_ptr()))
+    return o
+
+
+def clip_build(tables, w2c_R, w2c_t, start, date, decisions, T, obj_dim, noise=None, clip_index=None, seed=0, epoch=0):
+    """``vt_clip_build``: the batch of TrainDataCMotionFiller.get_item for B clips.  ``tables``: dict of float32 device tensors poses (N, 72), trans, roots,
+    obj_angles, obj_trans (N, 3); w2c_R (n_dates, 4, 3, 3), w2c_t (n_dates, 4, 3); start, date (B,) int32: clip b is frames [start[b], start[b] + T) of date
+    date[b]; ``decisions``: the dict of ``clip_draw`` (or explicit ones).  The noise of the augmentation is hashed from (seed, epoch, clip_index) unless ``noise``
+    (B, aug_num^2, 3) float32 is given (tests).  -> data_smpl, gt_smpl (B, T, 147), data_obj, gt_obj (B, T, obj_dim) float32, mask_obj, mask_smpl (B, T) bool."""
+    T, obj_dim = int(T), int(obj_dim)
+    if obj_dim not in (6, 9):
+        raise L.VtError(f"clip_build: obj_dim = {obj_dim}; 6 ('6d') or 9 ('9d')")
+    if not torch.is_tensor(tables.get("poses")) or tables["poses"].dim() != 2:
+        raise L.VtError("clip_build: tables['poses'] is an (N, 72) float32 device tensor")
+    dev, N = tables["poses"].device, tables["poses"].shape[0]
+    for k, w in CLIP_TABLES:
+        _clip_arg(f"clip_build: tables[{k!r}]", tables.get(k), torch.float32, (N, w), dev)
+    if T < 1 or N < T:
+        raise L.VtError(f"clip_build: T = {T} with {N} frames")
+    if not torch.is_tensor(w2c_R) or w2c_R.dim() != 4 or w2c_R.shape[0] < 1:
+        raise L.VtError("clip_build: w2c_R is an (n_dates, 4, 3, 3) float32 device tensor, n_dates >= 1")
+    nd = w2c_R.shape[0]
+    _clip_arg("clip_build: w2c_R", w2c_R, torch.float32, (nd, 4, 3, 3), dev)
+    _clip_arg("clip_build: w2c_t", w2c_t, torch.float32, (nd, 4, 3), dev)
+    if not torch.is_tensor(start) or start.dim() != 1 or start.numel() < 1:
+        raise L.VtError("clip_build: start is a (B,) int32 device tensor, B >= 1")
+    B = start.numel()
+    _clip_arg("clip_build: start", start, torch.int32, (B,), dev)
+    _clip_arg("clip_build: date", date, torch.int32, (B,), dev)
+    for k in CLIP_DECISIONS[:3]:
+        _clip_arg(f"clip_build: decisions[{k!r}]", decisions.get(k), torch.int32, (B,), dev)
+    au = decisions.get("aug_start")
+    aug_num = 0 if au is None else (au.shape[1] if torch.is_tensor(au) and au.dim() == 2 else -1)
+    if not 0 <= aug_num <= 64:
+        raise L.VtError("clip_build: decisions['aug_start'] is a (B, aug_num) int32 device tensor, aug_num <= 64")
+    if aug_num:
+        _clip_arg("clip_build: decisions['aug_start']", au, torch.int32, (B, aug_num), dev)
+        if noise is not None:
+            _clip_arg("clip_build: noise", noise, torch.float32, (B, aug_num * aug_num, 3), dev)
+        else:
+            _clip_arg("clip_build: clip_index", clip_index, torch.int32, (B,), dev)
+    seed, epoch = int(seed), int(epoch)
+    if not (0 <= seed < 1 << 64 and 0 <= epoch < 1 << 32):
+        raise L.VtError(f"clip_build: seed {seed} is a 64-bit, epoch {epoch} a 32-bit unsigned integer")
+    with torch.cuda.device(dev):
+        o = {"data_smpl": torch.empty((B, T, 147), device=dev), "data_obj": torch.empty((B, T, obj_dim), device=dev),
+             "gt_smpl": torch.empty((B, T, 147), device=dev), "gt_obj": torch.empty((B, T, obj_dim), device=dev),
+             "mask_obj": torch.empty((B, T), dtype=torch.bool, device=dev), "mask_smpl": torch.empty((B, T), dtype=torch.bool, device=dev)}
+        ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
+        L.check(L.lib().vt_clip_build(*[tables[k].data_ptr() for k, _ in CLIP_TABLES], N, w2c_R.data_ptr(), w2c_t.data_ptr(), nd, start.data_ptr(), date.data_ptr(),
+                                      decisions["kid"].data_ptr(), decisions["drop_len"].data_ptr(), decisions["start_fr"].data_ptr(), ptr(au if aug_num else None),
+                                      B, T, obj_dim, aug_num, ptr(noise if aug_num else None), ptr(clip_index if aug_num and noise is None else None), seed, epoch,
+                                      o["data_smpl"].data_ptr(), o["data_obj"].data_ptr(), o["gt_smpl"].data_ptr(), o["gt_obj"].data_ptr(),
+                                      o["mask_obj"].data_ptr(), o["mask_smpl"].data_ptr(), L.stream_ptr()))
+    return o
