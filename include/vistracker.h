@@ -993,6 +993,39 @@ int vt_layernorm_forward(const float *x, const float *weight, const float *bias,
 int vt_layernorm_backward(const float *d_y, const float *x, const double *stats, const float *weight, long M, int D, float *d_x, float *d_weight,
                           float *d_bias, int accumulate, float *workspace, void *stream);
 
+/* ---- HVOP-Net training, third block (infillhead.hip): the ends of the network and its objective.  fp32 row-major tensors over the M = B T rows; conventions
+ * and ARITHMETIC as formertrain.hip above (exact fp32 products on v_mfma_f32_16x16x4_f32 accumulated in a fixed order, sums over rows in chunks of 512 added
+ * in fp64 in chunk order, no atomics, the same bits on every call, a power-of-two scale of the incoming gradient scales every result bit for bit, clips
+ * independent).  An unsupported shape is VT_ERR_ARG and launches nothing; the size queries return -1.  Workspaces 8-byte aligned, nothing to initialise.
+ *
+ * vt_infill_proj_forward / _backward (feat_proj_smpl, feat_proj_obj of ConditionalMInfiller.forward, mfiller_cond.py:82-96, and their autograd backward): a table of
+ *   nprob <= 4 problems over the same M rows in one launch: ys[i] (M, n[i]) = xs[i] (M, kin[i]) weights[i]^T + biases[i]; kin in 1 .. 160, n % 16 == 0 in
+ *   16 .. 160.  xs .. ys, d_ys .. d_biases: HOST arrays of device pointers, kin / n HOST arrays.  Backward: d_weights[i] (n, kin) = d_ys[i]^T xs[i], d_biases[i] =
+ *   sum over rows of d_ys[i]; a NULL array or pointer skips that output, accumulate != 0 adds onto the outputs; no d_x (the inputs are data).
+ *   workspace: vt_infill_proj_workspace_floats(kin, n, nprob, M) floats.
+ * vt_infill_head_forward (the predictor of mfiller_cond.py:97-104 and, with `terms`, motion_losses of trainer_infiller.py:33-47): h = f W1^T + b1,
+ *   pred = leaky_relu(h, 0.01) W2^T + b2.  f (M, D), D % 16 == 0 in 16 .. 160; hidden % 16 == 0 in 16 .. 64; out_dim in 1 .. 16; T >= 3 (the reference's mean over
+ *   no acceleration row is NaN).  params: HOST array {W1 (hidden, D), b1, W2 (out_dim, hidden), b2}.  h (M, hidden) may be NULL (not saved).  terms (2 fp64,
+ *   device) may be NULL; else gt (M, out_dim) and a workspace of vt_infill_head_workspace_floats are needed and terms = {lw_pose mean |pred - gt|,
+ *   lw_accel mean |acc(pred) - acc(gt)|}, acc(a)[t] = a[t] - 2 a[t+1] + a[t+2] inside a clip, differences and sums in fp64 (per 16-row tile, the tiles of a
+ *   512-row chunk in order, the chunks in order).
+ * vt_infill_head_backward (the autograd backward of the same lines): with d_pred_in == NULL the gradient of loss_pos + loss_accel times `upstream`,
+ *   d_pred[t] = upstream (c_pos s[t] + c_acc (sa[t-2] - 2 sa[t-1] + sa[t])), s = sign(pred - gt), sa = sign(acc(pred) - acc(gt)), sign(0) = 0, rows outside the
+ *   clip dropped, c_pos = lw_pose / (B T out_dim), c_acc = lw_accel / (B (T - 2) out_dim), evaluated in fp64 and rounded once; else the given d_pred_in (terms
+ *   must then be NULL).  Then d_h = (d_pred W2) (h > 0 ? 1 : 0.01), d_f = d_h W1 and d_params, a HOST array in the order of params.  d_pred (always
+ *   overwritten), d_f, d_params and each of its pointers, terms may be NULL; accumulate != 0 adds onto d_f and d_params. */
+long vt_infill_proj_workspace_floats(const int *kin, const int *n, int nprob, long M);
+int vt_infill_proj_forward(const float *const *xs, const float *const *weights, const float *const *biases, const int *kin, const int *n, int nprob, long M,
+                           float *const *ys, void *stream);
+int vt_infill_proj_backward(const float *const *d_ys, const float *const *xs, const int *kin, const int *n, int nprob, long M, float *const *d_weights,
+                            float *const *d_biases, int accumulate, float *workspace, void *stream);
+long vt_infill_head_workspace_floats(int B, int T, int D, int hidden, int out_dim);
+int vt_infill_head_forward(const float *f, const float *const *params, const float *gt, int B, int T, int D, int hidden, int out_dim, double lw_pose,
+                           double lw_accel, float *pred, float *h, double *terms, float *workspace, void *stream);
+int vt_infill_head_backward(const float *d_pred_in, const float *gt, const float *pred, const float *h, const float *f, const float *const *params, int B, int T,
+                            int D, int hidden, int out_dim, double lw_pose, double lw_accel, double upstream, double *terms, float *d_pred, float *d_f,
+                            float *const *d_params, int accumulate, float *workspace, void *stream);
+
 /* ---- HVOP-Net training, the data set (clipdata.hip): the decisions of a clip and the assembly of a batch of clips on the device.  The packed data of all
  * sequences is fp32, concatenated over N frames: poses (N, 72) = columns [:69] + [111:114] of the SMPL-H pose (traindata_mfiller.py:102-105), trans, roots,
  * obj_angles, obj_trans (N, 3); w2c_R (n_dates, 4, 3, 3) and w2c_t (n_dates, 4, 3) are KinectTransform's world2local_R / world2local_t per date and camera.

@@ -10,7 +10,8 @@ NO_SCRATCH = ("query_kernel<2, 2, true>", "query_kernel<2, 2, false>", "query_ke
               "ovl_score_kernel<true>", "ovl_score_kernel<false>", "pm_dist_kernel", "pm_vertex_kernel", "pm_setup_kernel", "ll_loss_kernel", "ll_finish_kernel",
               "dect::feat_kernel", "dect::mlp_kernel<0>", "dect::mlp_kernel<1>", "dect::wgrad_kernel", "dect::finish_kernel", "formt::k_ln_qkv", "formt::k_attn_fwd", "formt::k_out_ff", "formt::k_ff_bwd",
               "formt::k_attn_bwd", "formt::k_qkv_bwd", "formt::k_wgrad", "formt::k_colsum", "formt::k_reduce", "formt::k_ln_fwd", "formt::k_ln_bwd",
-              "clipd::draw_kernel", "clipd::build_kernel<6>", "clipd::build_kernel<9>")
+              "clipd::draw_kernel", "clipd::build_kernel<6>", "clipd::build_kernel<9>",
+              "ifh::k_proj_fwd", "ifh::k_head_fwd", "ifh::k_head_bwd", "ifh::k_wgrad", "ifh::k_colsum", "ifh::k_reduce")
 
 rows, cur = [], None
 for line in sys.stdin:

@@ -219,6 +219,15 @@ SIGNATURES = {
     "vt_layernorm_backward_workspace_floats": (cl, [cl, ci]),
     "vt_layernorm_forward": (ci, [fp, fp, fp, cl, ci, fp, fp, vp]),
     "vt_layernorm_backward": (ci, [fp, fp, fp, fp, cl, ci, fp, fp, fp, ci, fp, vp]),
+    # csrc/infillhead.hip: xs, weights, biases, kin, n, nprob, M | ys, stream;  d_ys, xs, kin, n, nprob, M | d_weights, d_biases, accumulate, workspace, stream
+    "vt_infill_proj_workspace_floats": (cl, [vp, vp, ci, cl]),
+    "vt_infill_proj_forward": (ci, [vp, vp, vp, vp, vp, ci, cl, vp, vp]),
+    "vt_infill_proj_backward": (ci, [vp, vp, vp, vp, ci, cl, vp, vp, ci, fp, vp]),
+    # f, params[4], gt | B, T, D, hidden, out_dim | lw_pose, lw_accel | pred, h, terms, workspace, stream
+    "vt_infill_head_workspace_floats": (cl, [ci, ci, ci, ci, ci]),
+    "vt_infill_head_forward": (ci, [fp, vp, fp, ci, ci, ci, ci, ci, cd, cd, fp, fp, fp, fp, vp]),
+    # d_pred_in, gt, pred, h, f, params[4] | B, T, D, hidden, out_dim | lw_pose, lw_accel, upstream | terms, d_pred, d_f, d_params[4], accumulate, workspace, stream
+    "vt_infill_head_backward": (ci, [fp, fp, fp, fp, fp, vp, ci, ci, ci, ci, ci, cd, cd, cd, fp, fp, fp, vp, ci, fp, vp]),
     # csrc/clipdata.hip: clip_index, B | seed, epoch | T, multi_kinects, min_drop_len, max_drop_len, start_fr_min, start_fr_max, aug_num | kid, drop_len, start_fr, aug_start
     "vt_clip_draw": (ci, [fp, ci, C.c_ulonglong, C.c_uint, ci, ci, ci, ci, ci, ci, ci, fp, fp, fp, fp, vp]),
     # poses, trans, roots, obj_angles, obj_trans, N | w2c_R, w2c_t, n_dates | start, date, kid, drop_len, start_fr, aug_start | B, T, obj_dim, aug_num |

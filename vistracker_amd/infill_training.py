@@ -5,7 +5,8 @@
     trainer.trainer_infiller.TrainerInfiller.motion_losses / trainer_cinfiller.compute_loss      (trainer_infiller.py:33-47, trainer_cinfiller.py:30-44)
 
 The encoder layers run ``ops.former_layer_train`` (a taped HIP forward and a hand-written HIP backward per layer); the two input projections and the predictor MLP
-are six small GEMMs left to torch autograd.  Dropout masks come from the counter-based hash of csrc/dropout_hash.h, restated here for the per-layer seeds: a step
+are six small GEMMs left to torch autograd -- unless ``fused_ends`` is on: then the projections run ``ops.infill_proj_train`` and the predictor with the objective
+``ops.infill_head_train`` (csrc/infillhead.hip), and every gradient of a step comes from the project's own launches.  Dropout masks come from the counter-based hash of csrc/dropout_hash.h, restated here for the per-layer seeds: a step
 is a function of its ``seed``.  ``infill.py`` (inference) is untouched; ``export()`` hands the trained weights to it."""
 from __future__ import annotations
 
@@ -100,7 +101,7 @@ class TrainableConditionalMInfiller:
 
     ENCODERS = (("encoder_smpl.", "smpl"), ("encoder_obj.", "obj"), ("encoder_joint.", "joint"))
 
-    def __init__(self, sd, opt, dropout=None, device="cuda:0"):
+    def __init__(self, sd, opt, dropout=None, device="cuda:0", fused_ends=False):
         sd = infill._strip(sd); self.opt, self.dev = opt, torch.device(device)
         self.sd_keys = list(sd)
         dj = opt.d_model_smpl + opt.d_model_obj
@@ -112,10 +113,27 @@ class TrainableConditionalMInfiller:
                 getattr(opt, f"activation_{tag}"), getattr(opt, f"pre_norm_{tag}"), getattr(opt, f"dropout_{tag}") if dropout is None else dropout, self.dev, e)
         self.plain = {k: _leaf(sd[k], self.dev) for k in sd if not k.startswith(tuple(p for p, _ in self.ENCODERS))}
         self.n_head = len(opt.hidden_dims) + 1
+        self.fused_ends = bool(fused_ends)
+        self.ends_route = self._ends_route() if self.fused_ends else "torch: fused_ends is off"
 
     @classmethod
-    def from_state_dict(cls, sd, opt, dropout=None, device="cuda:0"):
-        return cls(sd, opt, dropout, device)
+    def from_state_dict(cls, sd, opt, dropout=None, device="cuda:0", fused_ends=False):
+        return cls(sd, opt, dropout, device, fused_ends)
+
+    def _ends_route(self):
+        """"hip" when the projections and the predictor are inside the contract of csrc/infillhead.hip, else "torch: <reason>" (the torch composition runs).
+        Decided once, on the widths alone: a batch the kernels refuse (T < 3, B T > 2^24) raises ``VtError`` from ``loss()``; it does not change the route."""
+        P = self.plain
+        if self.n_head != 2:
+            return f"torch: {self.n_head - 1} hidden layers in the predictor, the kernels take one"
+        for k in ("feat_proj_smpl.weight", "feat_proj_obj.weight"):
+            n, kin = P[k].shape
+            if not (1 <= kin <= 160 and 16 <= n <= 160 and n % 16 == 0):
+                return f"torch: {k} is {n} x {kin}; Kin in 1 .. 160 and N % 16 == 0 in 16 .. 160"
+        (hd, d), c = P["predictor.0.weight"].shape, P["predictor.2.weight"].shape[0]
+        if not (16 <= d <= 160 and d % 16 == 0 and 16 <= hd <= 64 and hd % 16 == 0 and 1 <= c <= 16):
+            return f"torch: predictor {d} -> {hd} -> {c}; D % 16 == 0 in 16 .. 160, hidden % 16 == 0 in 16 .. 64, out_dim in 1 .. 16"
+        return "hip"
 
     def train(self):
         for e in self.enc.values():
@@ -139,11 +157,34 @@ class TrainableConditionalMInfiller:
     def export(self):
         return infill.ConditionalMInfiller(self.state_dict(), self.opt, device=self.dev)
 
+    def features(self, data_smpl, mask_smpl, data_obj, mask_obj, seed=None):
+        """the joint encoder's output (B, T, d_model_smpl + d_model_obj), what the predictor reads"""
+        P = self.plain
+        xs, xo = data_smpl.to(self.dev).float(), data_obj.to(self.dev).float()
+        if self.ends_route == "hip":
+            ps, po = ops.infill_proj_train([xs.contiguous(), xo.contiguous()], [P["feat_proj_smpl.weight"], P["feat_proj_obj.weight"]],
+                                           [P["feat_proj_smpl.bias"], P["feat_proj_obj.bias"]])
+        else:
+            ps, po = F.linear(xs, P["feat_proj_smpl.weight"], P["feat_proj_smpl.bias"]), F.linear(xo, P["feat_proj_obj.weight"], P["feat_proj_obj.bias"])
+        fs = self.enc["smpl"](ps, mask_smpl.to(self.dev), seed)
+        fo = self.enc["obj"](po, mask_obj.to(self.dev), seed)
+        return self.enc["joint"](torch.cat([fs, fo], -1).contiguous(), None, seed)
+
+    def loss(self, batch, seed=None, lw=(1.0, 0.1)):
+        """-> (loss, loss_pos, loss_accel, pred): the objective of trainer_infiller.py:33-47 on a batch, fp32 device scalars; loss carries the graph.  With the
+        "hip" route the predictor and the objective are one ``ops.infill_head_train``; else the torch composition of ``__call__`` and ``motion_losses``."""
+        gt = batch["gt_obj"].to(self.dev).float()
+        if self.ends_route == "hip":
+            x = self.features(batch["data_smpl"], batch["mask_smpl"], batch["data_obj"], batch["mask_obj"], seed)
+            loss, lp, la, pred = ops.infill_head_train(x, gt.contiguous(), [self.plain[k] for k in ops.INFILL_HEAD_KEYS], *lw)
+            return loss.float(), lp.float(), la.float(), pred
+        pred = self(batch["data_smpl"], batch["mask_smpl"], batch["data_obj"], batch["mask_obj"], seed)
+        la, lp = motion_losses(gt, pred, *lw)
+        return lp + la, lp, la, pred
+
     def __call__(self, data_smpl, mask_smpl, data_obj, mask_obj, seed=None):
         P = self.plain
-        fs = self.enc["smpl"](F.linear(data_smpl.to(self.dev).float(), P["feat_proj_smpl.weight"], P["feat_proj_smpl.bias"]), mask_smpl.to(self.dev), seed)
-        fo = self.enc["obj"](F.linear(data_obj.to(self.dev).float(), P["feat_proj_obj.weight"], P["feat_proj_obj.bias"]), mask_obj.to(self.dev), seed)
-        x = self.enc["joint"](torch.cat([fs, fo], -1).contiguous(), None, seed)
+        x = self.features(data_smpl, mask_smpl, data_obj, mask_obj, seed)
         for i in range(self.n_head):
             x = F.linear(x, P[f"predictor.{2 * i}.weight"], P[f"predictor.{2 * i}.bias"])
             if i + 1 < self.n_head:
@@ -161,10 +202,13 @@ def motion_losses(gt, pred, lw_pose=1.0, lw_accel=0.1):
 
 class HVOPTrainer:
     """one training step of HVOP-Net (trainer_cinfiller.py:30-44 + the Adam / MultiStepLR of the reference's base trainer): zero grads, forward, ``motion_losses``,
-    one ``backward()``, one ``ops.FusedAdam.step()`` over the leaves.  Nothing in ``train_step`` waits on the host."""
+    one ``backward()``, one ``ops.FusedAdam.step()`` over the leaves.  Nothing in ``train_step`` waits on the host.  With ``fused_ends=True`` (off by default)
+    forward and objective are ``model.loss``: the projections, the predictor and both losses from csrc/infillhead.hip where ``model.ends_route`` is "hip";
+    ``train_step``, ``validate`` and ``train_epoch`` return the same fp32 device tensors either way."""
 
-    def __init__(self, sd, opt, lr=1e-4, milestones=(30, 40), gamma=0.1, dropout=None, lw_pose=1.0, lw_accel=0.1, device="cuda:0"):
-        self.model = TrainableConditionalMInfiller(sd, opt, dropout, device).train()
+    def __init__(self, sd, opt, lr=1e-4, milestones=(30, 40), gamma=0.1, dropout=None, lw_pose=1.0, lw_accel=0.1, device="cuda:0", fused_ends=False):
+        self.model = TrainableConditionalMInfiller(sd, opt, dropout, device, fused_ends).train()
+        self.fused_ends = bool(fused_ends)
         self.names = [k for k, _ in self.model.named_parameters()]
         self.optimizer = ops.FusedAdam([p for _, p in self.model.named_parameters()], lr=lr)
         self.lr0, self.milestones, self.gamma, self.lw = float(lr), tuple(milestones), float(gamma), (float(lw_pose), float(lw_accel))
@@ -178,6 +222,11 @@ class HVOPTrainer:
         """-> (loss (), sep_loss (2,) = [loss_pos, loss_accel]) device tensors of the objective BEFORE the update"""
         dev = self.model.dev
         self.optimizer.zero_grad()
+        if self.fused_ends:
+            loss, loss_pos, loss_accel, _ = self.model.loss(batch, seed, self.lw)
+            loss.backward()
+            self.optimizer.step()
+            return loss.detach(), torch.stack([loss_pos.detach(), loss_accel.detach()])
         pred = self.model(batch["data_smpl"], batch["mask_smpl"], batch["data_obj"], batch["mask_obj"], seed)
         loss_accel, loss_pos = motion_losses(batch["gt_obj"].to(dev).float(), pred, *self.lw)
         loss = loss_pos + loss_accel
@@ -186,6 +235,9 @@ class HVOPTrainer:
         return loss.detach(), torch.stack([loss_pos.detach(), loss_accel.detach()])
 
     def _loss(self, batch, seed=None):
+        if self.fused_ends:
+            loss, loss_pos, loss_accel, _ = self.model.loss(batch, seed, self.lw)
+            return loss, torch.stack([loss_pos, loss_accel])
         pred = self.model(batch["data_smpl"], batch["mask_smpl"], batch["data_obj"], batch["mask_obj"], seed)
         loss_accel, loss_pos = motion_losses(batch["gt_obj"].to(self.model.dev).float(), pred, *self.lw)
         return loss_pos + loss_accel, torch.stack([loss_pos, loss_accel])

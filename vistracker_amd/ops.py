@@ -1806,6 +1806,231 @@ def layernorm_train(x, weight, bias):
     return _LayerNormFn.apply(x, weight, bias)
 
 
+# ---- HVOP-Net training (csrc/infillhead.hip): the input projections, the predictor MLP and the motion objective -----------------------------------------
+INFILL_HEAD_KEYS = ("predictor.0.weight", "predictor.0.bias", "predictor.2.weight", "predictor.2.bias")
+_PROJ_RANGE = "1 .. 4 projections over the same rows, Kin in 1 .. 160, N % 16 == 0 in 16 .. 160"
+_HEAD_RANGE = "T >= 3, D % 16 == 0 in 16 .. 160, hidden % 16 == 0 in 16 .. 64, out_dim in 1 .. 16"
+
+
+def _ptr_array(ts):
+    return (C.c_void_p * len(ts))(*[None if t is None else L.dptr(t) for t in ts])
+
+
+def _dense32(what, name, t, shape=None, device=None, optional=False):
+    """a float32 contiguous device tensor of `shape`: the kernels read raw pointers"""
+    if t is None and optional:
+        return
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise L.VtError(f"{what}: {name} must be a device tensor; there is no CPU path")
+    if t.dtype != torch.float32:
+        raise L.VtError(f"{what}: {name} must be float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise L.VtError(f"{what}: {name} must be contiguous")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise L.VtError(f"{what}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if device is not None and t.device != device:
+        raise L.VtError(f"{what}: {name} on {t.device}, expected {device}")
+
+
+def _proj_check(what, xs, weights, biases):
+    """-> (M, kin, n) of a table of projections; every x is (..., Kin) over the same leading shape"""
+    if not (isinstance(xs, (list, tuple)) and isinstance(weights, (list, tuple)) and isinstance(biases, (list, tuple))) or not 1 <= len(xs) <= 4 \
+            or len(weights) != len(xs) or len(biases) != len(xs):
+        raise L.VtError(f"{what}: lists of the same length expected ({_PROJ_RANGE})")
+    for i, x in enumerate(xs):
+        _dense32(what, f"xs[{i}]", x)
+        if x.dim() < 2:
+            raise L.VtError(f"{what}: xs[{i}] must be (..., Kin)")
+    dev, lead = xs[0].device, tuple(xs[0].shape[:-1])
+    kin, n = [], []
+    for i, (x, w, b) in enumerate(zip(xs, weights, biases)):
+        if tuple(x.shape[:-1]) != lead:
+            raise L.VtError(f"{what}: xs[{i}] has leading shape {tuple(x.shape[:-1])}, xs[0] {lead}")
+        _dense32(what, f"weights[{i}]", w, device=dev)
+        if w.dim() != 2 or w.shape[1] != x.shape[-1]:
+            raise L.VtError(f"{what}: weights[{i}] has shape {tuple(w.shape)}, expected (N, {x.shape[-1]})")
+        _dense32(what, f"biases[{i}]", b, (w.shape[0],), dev)
+        kin.append(int(w.shape[1])); n.append(int(w.shape[0]))
+    M = xs[0].numel() // kin[0]
+    ka, na = (C.c_int * len(kin))(*kin), (C.c_int * len(n))(*n)
+    nws = int(L.lib().vt_infill_proj_workspace_floats(ka, na, len(kin), M))
+    if nws < 0:
+        raise L.VtError(f"{what}: unsupported shapes M {M} Kin {kin} N {n} ({_PROJ_RANGE})")
+    return M, ka, na, nws
+
+
+def infill_proj_forward(xs, weights, biases):
+    """vt_infill_proj_forward: [x (..., Kin) W^T + b for each problem] in one launch"""
+    M, ka, na, _ = _proj_check("infill_proj_forward", xs, weights, biases)
+    ys = [torch.empty(x.shape[:-1] + (w.shape[0],), dtype=torch.float32, device=x.device) for x, w in zip(xs, weights)]
+    with torch.cuda.device(xs[0].device):
+        L.check(L.lib().vt_infill_proj_forward(_ptr_array(xs), _ptr_array(weights), _ptr_array(biases), ka, na, len(xs), M, _ptr_array(ys), L.stream_ptr()))
+    return ys
+
+
+def infill_proj_backward(d_ys, xs, weights, biases, want=None, out=None, accumulate=False):
+    """vt_infill_proj_backward -> ([d_weight or None], [d_bias or None]).  ``weights`` / ``biases`` give the shapes only; ``want``: (flags of the weights, flags of
+    the biases), default all; ``out``: ([d_weight], [d_bias]) buffers to write / add into (None entries are skipped)."""
+    what = "infill_proj_backward"
+    M, ka, na, nws = _proj_check(what, xs, weights, biases)
+    if not isinstance(d_ys, (list, tuple)) or len(d_ys) != len(xs):
+        raise L.VtError(f"{what}: one d_y per projection expected")
+    dev = xs[0].device
+    for i, (d, x, w) in enumerate(zip(d_ys, xs, weights)):
+        _dense32(what, f"d_ys[{i}]", d, tuple(x.shape[:-1]) + (w.shape[0],), dev)
+    if out is not None:
+        dws, dbs = list(out[0]), list(out[1])
+        for i, (w, b) in enumerate(zip(weights, biases)):
+            _dense32(what, f"out d_weight[{i}]", dws[i], w.shape, dev, optional=True)
+            _dense32(what, f"out d_bias[{i}]", dbs[i], b.shape, dev, optional=True)
+    else:
+        ww, wb = ([True] * len(xs), [True] * len(xs)) if want is None else want
+        dws = [torch.empty_like(w) if f else None for w, f in zip(weights, ww)]
+        dbs = [torch.empty_like(b) if f else None for b, f in zip(biases, wb)]
+    ws = torch.empty(nws, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().vt_infill_proj_backward(_ptr_array(d_ys), _ptr_array(xs), ka, na, len(xs), M, _ptr_array(dws), _ptr_array(dbs), int(bool(accumulate)),
+                                                L.dptr(ws), L.stream_ptr()))
+    return dws, dbs
+
+
+class _InfillProjFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, n, *args):
+        xs, weights, biases = list(args[:n]), list(args[n:2 * n]), list(args[2 * n:])
+        ctx.n = n
+        ctx.save_for_backward(*xs, *weights, *biases)
+        return tuple(infill_proj_forward(xs, weights, biases))
+
+    @staticmethod
+    def backward(ctx, *d_ys):
+        n, t = ctx.n, ctx.saved_tensors
+        xs, weights, biases = list(t[:n]), list(t[n:2 * n]), list(t[2 * n:])
+        d_ys = [torch.zeros(x.shape[:-1] + (w.shape[0],), dtype=torch.float32, device=x.device) if d is None else d.contiguous() for d, x, w in zip(d_ys, xs, weights)]
+        need = ctx.needs_input_grad
+        dws, dbs = infill_proj_backward(d_ys, xs, weights, biases, want=(need[1 + n:1 + 2 * n], need[1 + 2 * n:]))
+        return (None,) + (None,) * n + tuple(dws) + tuple(dbs)
+
+
+def infill_proj_train(xs, weights, biases):
+    """the input projections of ConditionalMInfiller.forward (mfiller_cond.py:82-96) under autograd, all of them in one forward launch and three backward
+    launches: [x W^T + b]; gradients go to the weights and biases only (the inputs are data).  xs float32 contiguous device tensors (..., Kin) over the same rows.
+    No host wait in either direction."""
+    xs, weights, biases = list(xs), list(weights), list(biases)
+    _proj_check("infill_proj_train", xs, weights, biases)
+    return list(_InfillProjFn.apply(len(xs), *[x.detach() for x in xs], *weights, *biases))
+
+
+def _head_check(what, f, params, gt=None, need_gt=False):
+    _dense32(what, "f", f)
+    if f.dim() != 3:
+        raise L.VtError(f"{what}: f must be (B, T, D)")
+    B, T, D = (int(s) for s in f.shape)
+    if not isinstance(params, (list, tuple)) or len(params) != 4:
+        raise L.VtError(f"{what}: four parameters expected, in the order {INFILL_HEAD_KEYS}")
+    for k, q in zip(INFILL_HEAD_KEYS, params):
+        _dense32(what, k, q, device=f.device)
+    if params[0].dim() != 2 or params[2].dim() != 2:
+        raise L.VtError(f"{what}: the two weights must be matrices")
+    Hd, C_ = int(params[0].shape[0]), int(params[2].shape[0])
+    for k, q, s in zip(INFILL_HEAD_KEYS, params, ((Hd, D), (Hd,), (C_, Hd), (C_,))):
+        if tuple(q.shape) != s:
+            raise L.VtError(f"{what}: {k} has shape {tuple(q.shape)}, expected {s}")
+    nws = int(L.lib().vt_infill_head_workspace_floats(B, T, D, Hd, C_))
+    if nws < 0:
+        raise L.VtError(f"{what}: unsupported shape B {B} T {T} D {D} hidden {Hd} out_dim {C_} ({_HEAD_RANGE})")
+    if gt is not None or need_gt:
+        _dense32(what, "gt", gt, (B, T, C_), f.device)
+    return B, T, D, Hd, C_, nws
+
+
+def infill_head_forward(f, params, gt=None, lw_pose=1.0, lw_accel=0.1, save_h=True):
+    """vt_infill_head_forward -> (pred (B, T, out_dim), h (B, T, hidden) or None, terms or None).  With ``gt`` the two fp64 terms [loss_pos, loss_accel] of
+    trainer_infiller.py:33-47 are formed too; ``save_h=False`` is the forward-only mode of a validation."""
+    B, T, D, Hd, C_, nws = _head_check("infill_head_forward", f, params, gt)
+    dev = f.device
+    pred = torch.empty(B, T, C_, dtype=torch.float32, device=dev)
+    h = torch.empty(B, T, Hd, dtype=torch.float32, device=dev) if save_h else None
+    terms = torch.empty(2, dtype=torch.float64, device=dev) if gt is not None else None
+    ws = torch.empty(nws, dtype=torch.float32, device=dev) if gt is not None else None
+    with torch.cuda.device(dev):
+        L.check(L.lib().vt_infill_head_forward(L.dptr(f), _ptr_array(params), L.dptr(gt), B, T, D, Hd, C_, float(lw_pose), float(lw_accel), L.dptr(pred), L.dptr(h),
+                                               L.dptr(terms), L.dptr(ws), L.stream_ptr()))
+    return pred, h, terms
+
+
+def infill_head_backward(f, h, params, d_pred=None, gt=None, pred=None, lw_pose=1.0, lw_accel=0.1, upstream=1.0, want_terms=False, want_df=True, want=None, out=None,
+                         accumulate=False):
+    """vt_infill_head_backward -> (d_pred, d_f or None, [four gradients or None], terms or None).  With ``d_pred`` given it is the gradient to the prediction;
+    without, ``gt`` and ``pred`` are needed and d_pred is ``upstream`` times the gradient of loss_pos + loss_accel (``want_terms``: the two fp64 terms too).
+    ``want``: four flags (default all); ``out``: (d_f, [four]) buffers to write / add into."""
+    what = "infill_head_backward"
+    B, T, D, Hd, C_, nws = _head_check(what, f, params, gt, need_gt=d_pred is None)
+    dev = f.device
+    _dense32(what, "h", h, (B, T, Hd), dev)
+    if d_pred is None:
+        _dense32(what, "pred", pred, (B, T, C_), dev)
+        dp_out = torch.empty(B, T, C_, dtype=torch.float32, device=dev)
+    else:
+        _dense32(what, "d_pred", d_pred, (B, T, C_), dev)
+        if want_terms:
+            raise L.VtError(f"{what}: the objective's terms are not formed when d_pred is given")
+        dp_out = None
+    if out is not None:
+        d_f, grads = out[0], list(out[1])
+        _dense32(what, "out d_f", d_f, f.shape, dev, optional=True)
+        for k, g, q in zip(INFILL_HEAD_KEYS, grads, params):
+            _dense32(what, "out " + k, g, q.shape, dev, optional=True)
+    else:
+        want = [True] * 4 if want is None else list(want)
+        d_f = torch.empty_like(f) if want_df else None
+        grads = [torch.empty_like(q) if w else None for q, w in zip(params, want)]
+    terms = torch.empty(2, dtype=torch.float64, device=dev) if want_terms else None
+    ws = torch.empty(nws, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().vt_infill_head_backward(L.dptr(d_pred), L.dptr(gt), L.dptr(pred), L.dptr(h), L.dptr(f), _ptr_array(params), B, T, D, Hd, C_, float(lw_pose),
+                                                float(lw_accel), float(upstream), L.dptr(terms), L.dptr(dp_out), L.dptr(d_f), _ptr_array(grads),
+                                                int(bool(accumulate)), L.dptr(ws), L.stream_ptr()))
+    return (d_pred if dp_out is None else dp_out), d_f, grads, terms
+
+
+class _InfillHeadFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, f, gt, lw_pose, lw_accel, *params):
+        f = f.contiguous(); params = [q.contiguous() for q in params]
+        need = ctx.needs_input_grad
+        if need[0] or any(need[4:]):
+            pred, h, _ = infill_head_forward(f, params)
+            _, d_f, grads, terms = infill_head_backward(f, h, params, gt=gt, pred=pred, lw_pose=lw_pose, lw_accel=lw_accel, want_terms=True, want_df=need[0],
+                                                        want=need[4:])
+            ctx.grads = [d_f] + grads
+        else:
+            pred, _, terms = infill_head_forward(f, params, gt, lw_pose, lw_accel, save_h=False)
+            ctx.grads = [None] * 5
+        ctx.mark_non_differentiable(terms, pred)
+        return terms.sum(), terms, pred
+
+    @staticmethod
+    def backward(ctx, g, _gt, _gp):
+        g = g.to(torch.float32)
+        d = [None if t is None else t * g for t in ctx.grads]
+        return (d[0], None, None, None, *d[1:])
+
+
+def infill_head_train(f, gt, params, lw_pose=1.0, lw_accel=0.1):
+    """the predictor MLP (mfiller_cond.py:97-104) and motion_losses (trainer_infiller.py:33-47) under autograd -> (loss, loss_pos, loss_accel, pred): float64
+    device scalars (loss = loss_pos + loss_accel carries the graph, the two terms and pred (B, T, out_dim) float32 are not differentiable).  f (B, T, D) and the
+    four ``params`` (INFILL_HEAD_KEYS order) receive gradients; they are computed with the values for an upstream gradient of 1 and multiplied by the upstream
+    scalar in the backward.  Without a gradient to form (``torch.no_grad()``) only the values are computed and h is not saved.  No host wait."""
+    what = "infill_head_train"
+    if not (torch.is_tensor(f) and f.is_cuda):
+        raise L.VtError(f"{what}: f must be a device tensor; there is no CPU path")
+    f, params = f.contiguous(), list(params)
+    _head_check(what, f, params, gt, need_gt=True)
+    loss, terms, pred = _InfillHeadFn.apply(f, gt, float(lw_pose), float(lw_accel), *params)
+    return loss, terms[0], terms[1], pred
+
+
 # --------------------------------------------------------------------------------------------------
 # HVOP-Net training: the clip data set (csrc/clipdata.hip)
 # --------------------------------------------------------------------------------------------------
